@@ -1,10 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: particle-updates/s of the reference's test cases (BASELINE.json).
 
-Default: both headline configs of BASELINE.json in one invocation, each with its own W warmup and K timed steps:
-VE-SPH Sedov blast ``--init sedov -n 400`` (64 M particles, regular-lattice initial conditions) -> ``value`` /
-``ms_per_step``, then the Evrard collapse ``-n 200`` with Barnes-Hut self-gravity (glass ICs) -> ``evrard_value`` /
-``evrard_ms_per_step``. The Sedov state is freed before Evrard starts. ``--init CASE`` runs one case only.
+Default (a plain run): the headline config of BASELINE.json, the VE-SPH Sedov blast ``--init sedov -n 400`` (64 M
+particles, regular-lattice initial conditions) with W warmup and K timed steps -> ``value`` / ``ms_per_step``; nothing
+else is set up, measured or checked. ``--full`` also times BASELINE.json's second config in the same invocation, with
+its own W warmup and K timed steps: the Evrard collapse ``-n 200`` with Barnes-Hut self-gravity (glass ICs) ->
+``evrard_value`` / ``evrard_ms_per_step``. The Sedov state is freed before Evrard starts. ``--init CASE`` runs one
+case only.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step left for a caller of
+``Simulation.step``: the particle fields of a fixed, seeded sample of the owned particles (``DIR/<case>_<field>.npy``,
+float32/float64 as the field is stored, the sample's indices in ``<case>_index.npy``) and the globally reduced
+conserved quantities and time step (``<case>_conserved.npy``). The initial conditions are deterministic, so two
+builds run with the same arguments are comparable file by file.
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 the driver starts one process per
 GPU with torch.distributed.run. W untimed steps, then exactly K timed steps bracketed by barrier + device sync,
@@ -78,6 +86,12 @@ def main():
     ap.add_argument("--prop", default="ve")
     ap.add_argument("--device", default="auto", choices=["auto", "cuda", "cpu"])
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the second headline config (Evrard -n 200 with self-gravity -> evrard_* keys); "
+                         "a plain run times the Sedov case only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the particle fields and the conserved quantities after the last "
+                         "timed step as DIR/<case>_<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))
@@ -100,14 +114,15 @@ def main():
     else:
         device = torch.device("cpu")
 
-    # -n without --init applies to both cases (plumbing runs on small sizes)
+    # -n without --init applies to both cases (plumbing runs on small sizes); the headline pair names the metric,
+    # its second case is timed under --full only
     cases = [(args.init, args.n)] if args.init else [("sedov", args.n), ("evrard", args.n)]
-    results = [_run_case(init, n if n is not None else (200 if init == "evrard" else 400), args, comm, device)
-               for init, n in cases]
+    cases = [(init, n if n is not None else (200 if init == "evrard" else 400)) for init, n in cases]
+    results = [_run_case(init, n, args, comm, device) for init, n in (cases if args.full else cases[:1])]
     head = results[0]
     if rank == 0:
         out = {
-            "metric": _metric(results),
+            "metric": _metric(results + [dict(init=init, n=n, gravity=True) for init, n in cases[len(results):]]),
             "value": head["value"],
             "unit": "particle-updates/s",
             "n_gpus": size,
@@ -229,9 +244,43 @@ def _run_case(init: str, n: int, args, comm, device) -> dict:
         if device.type == "cuda":
             print(f"# max memory allocated {peak:.2f} GiB ({peak * 2**30 / max(d.numParticlesGlobal / size, 1):.0f} "
                   f"B/particle), held between steps {torch.cuda.memory_allocated() / 2**30:.2f} GiB", file=sys.stderr)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, init, sim, comm)
     del sim, prop, d
     gc.collect()
     return res
+
+
+DUMP_SAMPLE = 1 << 18  # particles per case: ~100 B each over the VE fields (6 fp64, 13 fp32), two cases -> 52 MB
+DUMP_SEED = 20240229
+
+
+def _dump_outputs(path: str, init: str, sim, comm) -> None:
+    """the state a caller of Simulation.step holds after the last timed step (host values already collected): every
+    allocated particle field that a step writes, at a seeded sample of the owned particles, and the conserved sums"""
+    import numpy as np
+
+    d, dom = sim.d, sim.domain
+    os.makedirs(path, exist_ok=True)
+    tag = init.replace(":", "_").replace("/", "_") + (f"_rank{comm.rank}" if comm.size > 1 else "")
+    first, last = dom.start_index(), dom.end_index()
+    owned = last - first
+    sample = DUMP_SAMPLE // comm.size  # (every rank writes its own share)
+    if owned > sample:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(owned, sample, replace=False))
+    else:
+        idx = np.arange(owned)
+    sel = torch.from_numpy(idx + first).to(d.device)
+    np.save(os.path.join(path, f"{tag}_index.npy"), idx.astype(np.float64))
+    names = sim.propagator.conserved_fields() + ["ax", "ay", "az", "du"]
+    for name in names:
+        if not d.is_allocated(name):
+            continue
+        v = d[name].index_select(0, sel).cpu()
+        v = v if v.dtype in (torch.float32, torch.float64) else v.to(torch.float64)
+        np.save(os.path.join(path, f"{tag}_{name}.npy"), v.numpy())
+    cons = [d.etot, d.ecin, d.eint, d.egrav, d.linmom, d.angmom, d.minDt, d.ttot, float(d.totalNeighbors)]
+    np.save(os.path.join(path, f"{tag}_conserved.npy"), np.asarray(cons, dtype=np.float64))
 
 
 if __name__ == "__main__":
