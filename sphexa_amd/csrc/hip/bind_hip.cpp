@@ -385,10 +385,16 @@ PYBIND11_MODULE(_sphx_hip, m)
           py::arg("vz") = 0, py::arg("eosTemp") = 0, py::arg("eosPrho") = 0, py::arg("eosC") = 0,
           py::arg("eosRho") = 0, py::arg("eosP") = 0);
     m.def("set_staged", [](unsigned mask) { setStaged(mask); },
-          "pair loops that run LDS-staged: bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum (hydro.hip, staged.h)");
+          "pair loops that run LDS-staged: bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum, 5 IAD and AV also on 256-thread "
+          "blocks (hydro.hip, staged.h)");
     m.def("staged_mask", []() { return stagedMask(); });
+    m.def("set_staged_counters", [](Ptr counters) { setStagedCounters(P<unsigned>(counters)); },
+          "two uint32 device counters of the block-union loops (blocks staged, blocks fallen back to the gathered "
+          "loop); 0: not counted (production)");
     m.def("set_list_masks", [](bool on) { setListMasks(on); },
           "store the per-slot staged-source masks in the list tables even without a staged loop (tests)");
+    m.def("list_masks_wanted", []() { return listMasksWanted(); },
+          "whether the search stores the slot masks: forced, or read by a staged loop of this run");
     m.def("set_pair_paths", [](bool kernelFixed, bool momBuf) { setPairPaths(kernelFixed, momBuf); },
           "pair-loop instances: the compile-time sinc^6 kernel function and the momentum loop's 32-bit buffer gathers "
           "(defaults on; tests compare them with the generic instances)", py::arg("kernel_fixed"), py::arg("mom_buf"));

@@ -185,11 +185,16 @@ void findNeighbors(int64_t first, int64_t last, const double* x, const double* y
 void setPairBlock(int block);
 //! pair-loop instances: compile-time sinc^6 kernel function, 32-bit buffer gathers of the momentum loop (both default on)
 void setPairPaths(bool kernelFixed, bool momBuf);
-//! pair loops that run LDS-staged (hydro.hip g_staged: bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum)
+//! pair loops that run LDS-staged (hydro.hip g_staged: bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum, 5 IAD and AV also
+//! on 256-thread blocks)
 void setStaged(unsigned mask);
 unsigned stagedMask();
+//! device counters of the block-union loops (tests): [0] blocks staged, [1] blocks fallen back; null: not counted
+void setStagedCounters(unsigned* counters);
 //! the search stores its per-slot staged-source masks (packed_list.hpp) also when no staged loop is enabled (tests)
 void setListMasks(bool on);
+//! whether the search stores the slot masks: forced (tests) or read by a staged loop of this run
+bool listMasksWanted();
 bool listMasksForced();
 //! fixed-point {x, y, z, m} records (QFrame of the box) of particles [0, n): the search and the XMass loop read them
 void packPosQ(int64_t n, const double* x, const double* y, const double* z, const float* m, const QFrame& q,

@@ -172,21 +172,54 @@ static const unsigned kPairMask = []
 
 void setPairBlock(int block) { g_pairBlock = block == 512 ? 512 : kBlock; }
 
-/* Loops that run LDS-staged (staged.h; bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum), fixed-point path only.
- * SPHX_STAGED overrides the default; setStaged (tests, A/B) at run time. */
+/* Loops that run LDS-staged (staged.h), fixed-point path only: bit 0 XMass (one group per workgroup, W waves; slower
+ * than the gathered loop, kept for A/B), bit 2 IAD and bit 3 the AV switches (block-union staging: the source union of
+ * the block's 8 or 4 groups in LDS, one wave per group, results bit-identical to the gathered loops). Bits 1 (Gradh)
+ * and 4 (momentum) have no staged loop: those loops gather. Bit 5: bits 2 and 3 also in runs on 256-thread blocks
+ * (setPairBlock: self-gravity); without it such runs gather, since the union of 4 groups (~1300 records on a lattice,
+ * ~1700 on a glass) does not fit the LDS of four blocks per CU (profiles/r7/staged_block/README.md).
+ * Default: IAD and AV (Sedov -n 400: IAD 15.4 -> 11.5 ms, AV 13.3 -> 9.4 ms). SPHX_STAGED overrides the default;
+ * setStaged (tests, A/B) at run time. */
 static unsigned g_staged = []
 {
     const char* e = std::getenv("SPHX_STAGED");
-    return e ? unsigned(std::strtoul(e, nullptr, 0)) : 0u;
+    return e ? unsigned(std::strtoul(e, nullptr, 0)) : 12u;
 }();
 
 void setStaged(unsigned mask) { g_staged = mask; }
 unsigned stagedMask() { return g_staged; }
 
+//! whether loop `loop` (2 IAD, 3 AV) runs its block-union kernel in this run
+static bool unionLoopOn(int loop)
+{
+    const bool big = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
+    return ((g_staged >> loop) & 1u) && (big || (g_staged & 32u));
+}
+
+// tests: blocks staged / fallen back by the block-union loops (one atomic per block); null in production
+static unsigned* g_stagedCounters = nullptr;
+void setStagedCounters(unsigned* counters) { g_stagedCounters = counters; }
+
+// union capacity (records) of the block-union loops per block size: 32-B records, the LDS of two 512-thread or four
+// 256-thread blocks per CU (4 waves per SIMD either way)
+#ifndef SPHX_STB_U512
+#define SPHX_STB_U512 2264
+#endif
+#ifndef SPHX_STB_U256
+#define SPHX_STB_U256 1128
+#endif
+template<int B>
+constexpr int kUnionCap = B == 512 ? SPHX_STB_U512 : SPHX_STB_U256;
+static_assert(sizeof(BlockUnionShared<8, kUnionCap<512>, 2>) * 2 <= 160 * 1024 &&
+                  sizeof(BlockUnionShared<4, kUnionCap<256>, 2>) * 4 <= 160 * 1024,
+              "16 waves per CU with the unions in LDS");
+
 // tests: the search stores the slot masks even when no staged loop runs (packed-list format checks)
 static bool g_listMasks = false;
 void setListMasks(bool on) { g_listMasks = on; }
 bool listMasksForced() { return g_listMasks; }
+// the search stores the slot masks (16 B per particle) only while a loop of this run reads them
+bool listMasksWanted() { return g_listMasks || (g_staged & 1u) || unionLoopOn(2) || unionLoopOn(3); }
 
 //! grid of a staged loop: one workgroup per target group
 inline unsigned gridStaged(const NbrArgs& a) { return unsigned((a.last - a.first + 63) / 64); }
@@ -698,30 +731,18 @@ __global__ __launch_bounds__(kBlock) void iadKernel(NbrArgs a, SphConsts sc, Box
         cij.p[k][i] = c[k];
 }
 
-//! @brief IAD matrix, then divv/curlv (+ velocity gradient) in the same kernel over the same neighbor list
-template<bool kAvS, class R, class G, int B = kBlock, int kKf = 0>
-__global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc, G box,
-                                                             const float* __restrict__ h,
-                                                             const float* __restrict__ kx,
-                                                             const R* __restrict__ rec,
-                                                             const float* __restrict__ wh, Six cij,
-                                                             float* __restrict__ divv, float* __restrict__ curlv,
-                                                             Six dV, int doGrad, float4* __restrict__ avS,
-                                                             SrcAvV* __restrict__ avOut, SrcMomQ* __restrict__ momOut,
-                                                             const float* __restrict__ cs, const float* __restrict__ mm,
-                                                             const float* __restrict__ prho,
-                                                             SrcMomSide* __restrict__ momSide = nullptr)
+/*! @brief epilogue of the IAD kernels: the target's results and, on the fixed-point records, the next loops' own
+ *         records. w: this wave's 64 x 5 float4 of LDS (row staging of the record writes; SrcIadQ only) */
+template<bool kAvS, class R>
+__device__ __forceinline__ void iadEpilogue(const NbrArgs& a, bool valid, int64_t i, const float* __restrict__ h,
+                                            const float* __restrict__ kx, const R* __restrict__ rec, Six cij,
+                                            float* __restrict__ divv, float* __restrict__ curlv, Six dV, int doGrad,
+                                            float4* __restrict__ avS, SrcAvV* __restrict__ avOut,
+                                            SrcMomQ* __restrict__ momOut, const float* __restrict__ cs,
+                                            const float* __restrict__ mm, const float* __restrict__ prho,
+                                            SrcMomSide* __restrict__ momSide, const float (&c)[6], const float (&g)[6],
+                                            float dvi, float cvi, const float (&S)[3], float4* w)
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
-    int64_t i;
-    PackedLane pl;
-    unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
-    float c[6], g[6], dvi, cvi, S[3];
-    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], coopOf(rec, tile, i, a), kf, c, dvi,
-                                cvi, g, S);
-    });
     if (valid)
     {
         for (int k = 0; k < 6; ++k)
@@ -740,8 +761,6 @@ __global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc,
         // stride; staged through LDS, the wave writes its 64 contiguous records as whole 1-KiB rows instead.
         if ((avOut || momOut) && ballot(valid))
         {
-            __shared__ float4 stage[B / 64][64 * 5];
-            float4* w       = stage[threadIdx.x >> 6];
             const int lane  = threadIdx.x & 63;
             const int64_t i0 = int64_t(__builtin_amdgcn_readfirstlane(int(i - a.first))) + a.first; // lane 0 is valid
             const int nv     = int(min(int64_t(64), int64_t(a.last) - i0));
@@ -830,6 +849,77 @@ __global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc,
     }
 }
 
+//! @brief IAD matrix, then divv/curlv (+ velocity gradient) in the same kernel over the same neighbor list
+template<bool kAvS, class R, class G, int B = kBlock, int kKf = 0>
+__global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc, G box,
+                                                             const float* __restrict__ h,
+                                                             const float* __restrict__ kx,
+                                                             const R* __restrict__ rec,
+                                                             const float* __restrict__ wh, Six cij,
+                                                             float* __restrict__ divv, float* __restrict__ curlv,
+                                                             Six dV, int doGrad, float4* __restrict__ avS,
+                                                             SrcAvV* __restrict__ avOut, SrcMomQ* __restrict__ momOut,
+                                                             const float* __restrict__ cs, const float* __restrict__ mm,
+                                                             const float* __restrict__ prho,
+                                                             SrcMomSide* __restrict__ momSide = nullptr)
+{
+    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
+    int64_t i;
+    PackedLane pl;
+    unsigned n;
+    const bool valid = targetOf<B>(a, i, pl, n);
+    float c[6], g[6], dvi, cvi, S[3];
+    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
+        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], coopOf(rec, tile, i, a), kf, c, dvi,
+                                cvi, g, S);
+    });
+    float4* w = nullptr;
+    if constexpr (std::is_same_v<R, SrcIadQ>)
+    {
+        __shared__ float4 stage[B / 64][64 * 5];
+        w = stage[threadIdx.x >> 6];
+    }
+    iadEpilogue<kAvS>(a, valid, i, h, kx, rec, cij, divv, curlv, dV, doGrad, avS, avOut, momOut, cs, mm, prho, momSide,
+                      c, g, dvi, cvi, S, w);
+}
+
+/*! @brief iadDivvCurlvKernel on SrcIadQ records with the block's source union staged in LDS (staged.h, block-union
+ *         staging; a block whose union does not fit runs the gathered loop). Same sums in the same order. The
+ *         epilogue's row staging reuses the records' LDS. */
+template<bool kAvS, int B, int kKf, int UCAP>
+__global__ __launch_bounds__(B) void iadDivvCurlvUnionKernel(NbrArgs a, SphConsts sc, QFrame box,
+                                                             const float* __restrict__ h,
+                                                             const float* __restrict__ kx,
+                                                             const SrcIadQ* __restrict__ rec,
+                                                             const float* __restrict__ wh, Six cij,
+                                                             float* __restrict__ divv, float* __restrict__ curlv,
+                                                             Six dV, int doGrad, float4* __restrict__ avS,
+                                                             SrcAvV* __restrict__ avOut, SrcMomQ* __restrict__ momOut,
+                                                             const float* __restrict__ cs, const float* __restrict__ mm,
+                                                             const float* __restrict__ prho,
+                                                             SrcMomSide* __restrict__ momSide, unsigned* counters)
+{
+    using Ld = BlockUnionLoader<SrcIadQ, B / 64, UCAP>;
+    __shared__ typename Ld::Shared sh;
+    static_assert(sizeof(sh.rec) >= sizeof(float4) * (B / 64) * 64 * 5, "the epilogue's rows fit the records' LDS");
+    int64_t i;
+    PackedLane pl;
+    BlockLane bl;
+    unsigned n;
+    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
+    const bool staged = stageBlockUnion<SrcIadQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
+    if (!staged) loadChunkTable(bl, pl, sh);
+    float c[6], g[6], dvi, cvi, S[3];
+    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
+        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], Ld{rec, &sh, &bl, staged}, kf, c, dvi,
+                                cvi, g, S);
+    });
+    __syncthreads(); // every wave is done with the records (or chunk tables)
+    float4* w = reinterpret_cast<float4*>(sh.rec) + (threadIdx.x >> 6) * 64 * 5;
+    iadEpilogue<kAvS>(a, valid, i, h, kx, rec, cij, divv, curlv, dV, doGrad, avS, avOut, momOut, cs, mm, prho, momSide,
+                      c, g, dvi, cvi, S, w);
+}
+
 __global__ __launch_bounds__(kBlock) void avSwitchesKernel(NbrArgs a, SphConsts sc, Box box,
                                                            const float* __restrict__ h, Six cij,
                                                            const SrcIad* __restrict__ rec,
@@ -896,6 +986,44 @@ __global__ __launch_bounds__(B) void avSwitchesVKernel(NbrArgs a, SphConsts sc, 
     float al;
     withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
         al = avSwitchesVJLoop(unsigned(i), sc.K, q, &pl, 0, n, h[i], ci, divv[i], S, coopOf(rec, tile, i, a), kf, dt,
+                              sc.alphamin, sc.alphamax, sc.decayConstant, alpha[i]);
+    });
+    if (!valid) return;
+    alphaOut[i] = al;
+    if (momSide) momSide[i].alpha = al;
+    else if (momOut) momOut[i].alpha = al;
+}
+
+/*! @brief avSwitchesVKernel with the block's source union staged in LDS (staged.h, block-union staging; a block whose
+ *         union does not fit runs the gathered loop). Same sums in the same order. */
+template<int B, int kKf, int UCAP>
+__global__ __launch_bounds__(B) void avSwitchesVUnionKernel(NbrArgs a, SphConsts sc, QFrame q,
+                                                            const float* __restrict__ h, Six cij,
+                                                            const SrcAvV* __restrict__ rec,
+                                                            const float* __restrict__ divv,
+                                                            const float4* __restrict__ avS,
+                                                            const float* __restrict__ wh, double dt,
+                                                            const float* __restrict__ alpha,
+                                                            float* __restrict__ alphaOut, const double* dtDev,
+                                                            SrcMomQ* __restrict__ momOut,
+                                                            SrcMomSide* __restrict__ momSide, unsigned* counters)
+{
+    using Ld = BlockUnionLoader<SrcAvV, B / 64, UCAP>;
+    __shared__ typename Ld::Shared sh;
+    int64_t i;
+    PackedLane pl;
+    BlockLane bl;
+    unsigned n;
+    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
+    const bool staged = stageBlockUnion<SrcAvV, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
+    if (!staged) loadChunkTable(bl, pl, sh);
+    if (dtDev) dt = *dtDev;
+    float ci[6]    = {cij.p[0][i], cij.p[1][i], cij.p[2][i], cij.p[3][i], cij.p[4][i], cij.p[5][i]};
+    const float4 s = avS[i - a.first];
+    const float S[3] = {s.x, s.y, s.z};
+    float al;
+    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
+        al = avSwitchesVJLoop(unsigned(i), sc.K, q, &pl, 0, n, h[i], ci, divv[i], S, Ld{rec, &sh, &bl, staged}, kf, dt,
                               sc.alphamin, sc.alphamax, sc.decayConstant, alpha[i]);
     });
     if (!valid) return;
@@ -1431,6 +1559,29 @@ void iadDivvCurlv(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t
                    });
         // fixed-point path: also the S_i of the AV loop (avSwitchesVJLoop) when a workspace is given, and the next
         // loops' own records (avOut / momOut)
+        if (unionLoopOn(2))
+        {
+            withPairBlock([&](auto bc)
+                          {
+                              constexpr int B = decltype(bc)::value;
+                              withKf(sc, [&](auto kk)
+                              {
+                                  constexpr int KK = decltype(kk)::value;
+                                  if (avS)
+                                      iadDivvCurlvUnionKernel<true, B, KK, kUnionCap<B>><<<gridT(a, B), B, 0, s>>>(
+                                          withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
+                                          dV[0] != nullptr, (float4*)avS, (SrcAvV*)avOut, (SrcMomQ*)momOut, cs, m, prho,
+                                          momSide, g_stagedCounters);
+                                  else
+                                      iadDivvCurlvUnionKernel<false, B, KK, kUnionCap<B>><<<gridT(a, B), B, 0, s>>>(
+                                          withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
+                                          dV[0] != nullptr, nullptr, nullptr, (SrcMomQ*)momOut, cs, m, prho, momSide,
+                                          g_stagedCounters);
+                              });
+                          }, 2);
+            SPHX_LAUNCH_CHECK();
+            return;
+        }
         withPairBlock([&](auto bc)
                       {
                           constexpr int B = decltype(bc)::value;
@@ -1479,6 +1630,23 @@ void avSwitches(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t n
                        packAvVKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, kx, vx, vy, vz, xm, c, divv,
                                                                            q, (SrcAvV*)rec);
                    });
+        if (unionLoopOn(3))
+        {
+            withPairBlock([&](auto bc)
+                          {
+                              constexpr int B = decltype(bc)::value;
+                              withKf(sc, [&](auto kk)
+                                     {
+                                         avSwitchesVUnionKernel<B, decltype(kk)::value, kUnionCap<B>>
+                                             <<<gridT(a, B), B, 0, s>>>(
+                                                 withTot(a, ntot), sc, q, h, cc, (const SrcAvV*)rec, divv,
+                                                 (const float4*)avS, wh, dt, alpha, alphaOut, dtDev, (SrcMomQ*)momOut,
+                                                 momSideOf(momOut, ntot, momSplit), g_stagedCounters);
+                                     });
+                          }, 3);
+            SPHX_LAUNCH_CHECK();
+            return;
+        }
         withPairBlockL<SPHX_AV_BLOCK>([&](auto bc)
                       {
                           constexpr int B = decltype(bc)::value;

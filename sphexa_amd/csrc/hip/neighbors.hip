@@ -1229,7 +1229,7 @@ void findNeighbors(int64_t first, int64_t last, const double* x, const double* y
                        ovBase + (unsigned long long)kRowStripes * ovStride,
                        stats + 8,
                        // the slot masks cost a table row per group (16 B/particle): only while a staged loop reads them
-                       stagedMask() != 0u || listMasksForced() ? 1 : 0};
+                       listMasksWanted() ? 1 : 0};
     int64_t spillMemOff, total;
     scratchLayout(n, spillMemOff, total);
     int32_t* splitList = static_cast<int32_t*>(scratch);

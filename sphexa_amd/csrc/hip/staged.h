@@ -1,5 +1,7 @@
 /*! LDS-staged SPH pair loops (gfx950): the sources of a 64-target group are copied into LDS once per group and every
- *  neighbor step reads its record there instead of gathering it from L2.
+ *  neighbor step reads its record there instead of gathering it from L2. Two designs: one workgroup per group (below;
+ *  XMass, slower than gathering, kept for A/B) and, in the second half of this file, the union of a block's 4 or 8
+ *  groups staged once per block with one wave per group (IAD and AV: the production loops).
  *
  * Parity: the loops themselves are the reference's hydro_ve kernels (sph/include/sph/hydro_ve/*_kern.hpp, e.g.
  * momentum_energy_kern.hpp:113-222), here through the shared J-loops of sphx/sph_math.hpp. What differs is where
@@ -377,6 +379,316 @@ __device__ void reduceAcrossMax(const StagedLoader<R, W, UCAP, kSide>& ld, T&...
         };
         ((v = total(k++)), ...);
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Block-union staging: the source union of the NG SFC-consecutive groups of a block, staged in LDS once per block
+// ------------------------------------------------------------------------------------------------------------
+
+/*! One wave = one 64-target group, as in the gathered loops (no list rows split across waves, the per-target
+ *  summation order is the gathered loops' order: results are bit-identical). The NG groups of a block are neighbors
+ *  on the SFC and name mostly the same chunks: chunk bases are leaf-relative, so a chunk has the same base c0 in
+ *  every group that staged it. Prologue (all waves):
+ *    1. every wave reads its group's chunk bases and slot masks (one slot per lane, up to kBuSlots slots) and inserts
+ *       them into an LDS hash keyed by c0 (compare-and-swap on the key, OR of the masks);
+ *    2. one thread per hash entry: popcount of the merged mask, block-wide prefix sum -> the entry's first record
+ *       position; the non-empty entries are listed densely;
+ *    3. every lane looks its slot's merged entry up and keeps {c0, base, mask} in registers; the waves copy the
+ *       records of the dense entries (lane k = particle c0 + k: coalesced) to their positions;
+ *    4. the hash is dead: its memory becomes the per-wave slot tables (one 16-B entry per slot).
+ *  Neighbor step: code (slot, off) -> table entry (one ds_read_b128) -> position base + popcount(mask below off)
+ *  -> record (RC x ds_read_b128). The index c0 + off serves the self test only. Slot 0 (padding codes: the target
+ *  itself) has the entry {group's first particle, 0, 0}: it decodes to the target and is skipped like it.
+ *  A block falls back, as a whole, to the gathered loop in the same kernel when the merged union exceeds UCAP records,
+ *  a group has more than kBuSlots slots, the lists were searched without slot masks (T == Tc), a table value is out of
+ *  range or the hash is full. The chunk tables of the gathered loop share the records' LDS. */
+constexpr unsigned kBuSlots = 64;
+constexpr uint32_t kBuEmpty = 0xFFFFFFFFu;
+
+//! the group of one wave: its table and what blockTargetOf read from it
+struct BlockLane
+{
+    const int32_t* tab;     // group table
+    const int32_t* rowsInt; // row pool
+    unsigned nch, Tc, T;    // chunk slots (0: no group), chunk-base rows, table rows
+    unsigned gfirst;        // first particle of the group
+
+    __device__ __forceinline__ int32_t rowOf(unsigned o) const
+    {
+        return *(const __attribute__((address_space(4))) int32_t*)(tab + 2 + o);
+    }
+};
+
+template<int NG, int UCAP, int RC>
+struct BlockUnionShared
+{
+    static constexpr int HS = 64 * NG; // hash entries = threads of the block = slot-table entries
+    union
+    {
+        uint4 rec[(UCAP + 1) * RC];    // (one record past the capacity: a code whose mask bit is missing stays inside)
+        uint32_t ctab[NG][kChunkCap];  // gathered fallback: the groups' chunk tables
+    };
+    uint4 tab[HS];       // prologue: hash {c0, base, mask lo, mask hi}; loops: slot tables [wave][slot]
+    uint16_t dense[HS];  // the non-empty hash entries
+    unsigned wsum[NG];   // per-wave totals of the scan (records | entries << 16)
+    unsigned fail;
+};
+
+/*! @brief as targetOf (hydro.hip) without the chunk table: target i (clamped past the last particle; the return value
+ *         tells whether it is valid), its list rows, the group's table header */
+template<int B>
+__device__ __forceinline__ bool blockTargetOf(const NbrArgs& a, int64_t& i, PackedLane& pl, unsigned& n, BlockLane& bl)
+{
+    const unsigned lb   = xcdRemap(blockIdx.x, gridDim.x);
+    const int64_t t     = int64_t(lb) * B + threadIdx.x;
+    i                   = a.first + t;
+    const int64_t g     = t >> 6;
+    const int64_t G     = (a.last - a.first + 63) / 64;
+    const unsigned lane = threadIdx.x & 63;
+    bl.tab              = a.nidx + g * int64_t(packedTableInts(a.ngmax));
+    bl.rowsInt          = a.nidx + packedTableRegion(G, a.ngmax);
+    bl.nch = bl.Tc = bl.T = 0;
+    bl.gfirst             = unsigned(a.first + g * 64);
+    pl.nblk               = 0;
+    if (g < G) // wave-uniform: waves past the last group have no table
+    {
+        pl.nblk          = unsigned(*(const __attribute__((address_space(4))) int32_t*)(bl.tab));
+        const unsigned w = unsigned(*(const __attribute__((address_space(4))) int32_t*)(bl.tab + 1));
+        bl.nch           = min(tableWordNch(w), kChunkCap);
+        bl.Tc            = tableWordTc(w);
+        bl.T             = tableWordT(w);
+    }
+    pl.tab  = bl.tab + 2 + bl.T;
+    pl.rows = reinterpret_cast<const int4*>(bl.rowsInt) + lane;
+    pl.ctab = nullptr;
+#ifdef SPHX_DEVICE_CHECKS
+    pl.ntot = a.ntot;
+    SPHX_DCHECK(pl.nblk <= listBlocksMax(a.ngmax), 1);
+    pl.nblk = min(pl.nblk, listBlocksMax(a.ngmax));
+#endif
+    if (i >= a.last)
+    {
+        i       = a.last - 1;
+        pl.self = unsigned(i);
+        n       = 0;
+        return false;
+    }
+    pl.self = unsigned(i);
+    const int cnt = a.nc[i] - 1;
+    n             = unsigned(cnt < 0 ? 0 : (unsigned(cnt) < a.ngmax ? cnt : a.ngmax));
+    return true;
+}
+
+//! @brief the gathered fallback of a block-union kernel: the wave's chunk table into the LDS the records would use
+template<int NG, int UCAP, int RC>
+__device__ __forceinline__ void loadChunkTable(const BlockLane& bl, PackedLane& pl, BlockUnionShared<NG, UCAP, RC>& sh)
+{
+    const unsigned lane = threadIdx.x & 63;
+    uint32_t* ctab      = sh.ctab[threadIdx.x >> 6];
+    for (unsigned e = lane; e < bl.nch; e += 64)
+        ctab[e] = uint32_t(bl.rowsInt[size_t(bl.rowOf(e >> 8)) * 256 + (e & 255)]);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    pl.ctab = ctab;
+}
+
+/*! @brief the prologue (file comment above; all threads of the block call it): true if the block's union is staged
+ *         (block-uniform), false if the block takes the gathered loop (nothing of sh is in use then) */
+template<class R, int NG, int UCAP>
+__device__ bool stageBlockUnion(const BlockLane& bl, const R* __restrict__ rec, unsigned ntot,
+                                BlockUnionShared<NG, UCAP, int(sizeof(R) / 16)>& sh, unsigned* counters)
+{
+    constexpr int RC = int(sizeof(R) / 16);
+    constexpr int HS = 64 * NG;
+    static_assert((HS & (HS - 1)) == 0, "hash size is a power of two");
+    // at most NG * (kBuSlots - 1) < HS keys are inserted: the hash always has a free entry
+    static_assert(UCAP + 64 < 65536 && NG * (kBuSlots - 1) * 64 < 65536, "the scan packs two 16-bit counts");
+    const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    sh.tab[t] = make_uint4(kBuEmpty, 0u, 0u, 0u);
+    if (t == 0) sh.fail = 0u;
+    __syncthreads();
+    // 1. this wave's slots (slot = lane; slot 0 holds the padding codes only and is not staged)
+    const bool masks  = bl.T >= bl.Tc + maskTabRows(bl.nch) && bl.T > bl.Tc;
+    const bool waveOk = bl.nch <= kBuSlots && (bl.nch <= 1u || masks);
+    const bool mine   = waveOk && lane >= 1u && lane < bl.nch;
+    bool bad          = !waveOk;
+    unsigned e        = 0;
+    if (mine)
+    {
+        const uint32_t cb = uint32_t(bl.rowsInt[size_t(bl.rowOf(0)) * 256 + lane]);
+        const int32_t* mr = bl.rowsInt + size_t(bl.rowOf(bl.Tc)) * 256 + 2 * lane;
+        uint32_t lo = uint32_t(mr[0]), hi = uint32_t(mr[1]);
+        if (cb >= ntot) bad = true; // (also excludes the empty key)
+        else
+        {
+            // sources past the last record are never staged
+            const unsigned avail = min(ntot - cb, 64u);
+            const uint64_t keep  = avail >= 64u ? ~0ull : ((1ull << avail) - 1ull);
+            lo &= uint32_t(keep);
+            hi &= uint32_t(keep >> 32);
+            unsigned hsh = (cb * 2654435761u) >> (32 - __builtin_ctz(unsigned(HS)));
+            bool done    = false;
+            for (int tries = 0; tries < HS && !done; ++tries)
+            {
+                const uint32_t old = atomicCAS(&sh.tab[hsh].x, kBuEmpty, cb);
+                if (old == kBuEmpty || old == cb)
+                {
+                    if (lo) atomicOr(&sh.tab[hsh].z, lo);
+                    if (hi) atomicOr(&sh.tab[hsh].w, hi);
+                    e    = hsh;
+                    done = true;
+                }
+                else hsh = (hsh + 1u) & unsigned(HS - 1);
+            }
+            if (!done) bad = true;
+        }
+    }
+    if (bad) sh.fail = 1u;
+    __syncthreads();
+    // 2. positions: exclusive scan of the merged popcounts over the hash entries (and of the non-empty entries)
+    uint4 ent          = sh.tab[t];
+    const bool used    = ent.x != kBuEmpty;
+    const unsigned cnt = used ? unsigned(__popc(ent.z) + __popc(ent.w)) : 0u;
+    const unsigned pk  = cnt | (used ? 1u << 16 : 0u);
+    unsigned incl      = pk;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+        const unsigned up = unsigned(__shfl_up(int(incl), o));
+        if (int(lane) >= o) incl += up;
+    }
+    if (lane == 63) sh.wsum[wave] = incl;
+    __syncthreads();
+    unsigned before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < NG; ++w)
+    {
+        const unsigned s = sh.wsum[w];
+        before += unsigned(w) < wave ? s : 0u;
+        total += s;
+    }
+    const unsigned excl = before + incl - pk;
+    const unsigned nrec = total & 0xFFFFu, nent = total >> 16;
+    const bool staged   = sh.fail == 0u && nrec <= unsigned(UCAP);
+    if (counters && t == 0) atomicAdd(&counters[staged ? 0 : 1], 1u);
+    if (!staged)
+    {
+        __syncthreads(); // every thread has read fail and wsum: the chunk tables may overwrite the union's LDS
+        return false;
+    }
+    if (used)
+    {
+        sh.tab[t].y               = excl & 0xFFFFu;
+        sh.dense[excl >> 16]      = uint16_t(t);
+    }
+    __syncthreads();
+    // 3. this lane's slot entry; the records of the dense entries, a wave per entry
+    uint4 slotEnt = make_uint4(bl.gfirst, 0u, 0u, 0u); // slot 0 and slots past the table
+    if (mine) slotEnt = sh.tab[e];
+    for (unsigned k = wave; k < nent; k += NG)
+    {
+        const uint4 en   = sh.tab[sh.dense[k]];
+        const uint64_t m = uint64_t(en.w) << 32 | en.z;
+        if ((m >> lane) & 1)
+        {
+            const unsigned p = en.y + unsigned(__popcll(m & lanemaskLt()));
+            const uint4* src = reinterpret_cast<const uint4*>(rec) + size_t(en.x + lane) * RC;
+#pragma unroll
+            for (int c = 0; c < RC; ++c)
+                sh.rec[p * RC + c] = src[c];
+        }
+    }
+    __syncthreads();
+    // 4. the hash becomes the slot tables
+    sh.tab[t] = slotEnt;
+    __syncthreads();
+    return true;
+}
+
+/*! @brief the neighbor loop of a staged block: forEachNeighborDirect (sph_math.hpp) with the records read from the
+ *         block's LDS union. Same entries, same order; the target itself and padding codes are skipped. */
+template<class R, int NG, int UCAP, class F>
+__device__ void forEachNeighborUnion(const PackedLane& pl, const BlockLane& bl,
+                                     const BlockUnionShared<NG, UCAP, int(sizeof(R) / 16)>& sh, F&& f)
+{
+    constexpr int RC    = int(sizeof(R) / 16);
+    const unsigned nblk = pl.nblk;
+    if (nblk == 0) return;
+    const uint4* wtab = sh.tab + (threadIdx.x >> 6) * 64;
+    int4 w            = pl.block(0);
+    auto batch = [&](int w0, int w1)
+    {
+        const uint32_t ws[2] = {uint32_t(w0), uint32_t(w1)};
+        unsigned j[4];
+        R rr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+        {
+            const uint32_t code = (ws[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;
+            // (a staged group has at most kBuSlots slots: the masked slot stays inside the wave's table)
+            const unsigned slot = code & (kBuSlots - 1u), off = code >> kChunkSlotBits;
+            const uint4 en      = wtab[slot];
+            const uint32_t below = (1u << (off & 31u)) - 1u;
+            const bool upper     = off >= 32u;
+            const uint32_t lo = upper ? en.z : en.z & below, hi = upper ? en.w & below : 0u;
+            unsigned p        = en.y + unsigned(__popc(lo)) + unsigned(__popc(hi));
+            j[u]              = en.x + off;
+#ifdef SPHX_DEVICE_CHECKS
+            const bool ok = (code & kChunkSlotMask) < max(bl.nch, 1u) && p < unsigned(UCAP) &&
+                            ((code & kChunkSlotMask) != 0u || j[u] == pl.self);
+            SPHX_DCHECK(ok, 0);
+            if (!ok)
+            {
+                p    = 0u;
+                j[u] = pl.self;
+            }
+#endif
+            uint4 o4[RC];
+#pragma unroll
+            for (int c = 0; c < RC; ++c)
+                o4[c] = sh.rec[p * RC + c];
+            float4 o[RC];
+#pragma unroll
+            for (int c = 0; c < RC; ++c)
+                o[c] = make_float4(__uint_as_float(o4[c].x), __uint_as_float(o4[c].y), __uint_as_float(o4[c].z),
+                                   __uint_as_float(o4[c].w));
+            rr[u] = stagedUnpack<R>(o);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+        {
+            pinRegs(rr[u]);
+            if (j[u] != pl.self) f(j[u], rr[u]);
+        }
+    };
+    for (unsigned b = 0; b < nblk; ++b)
+    {
+        const int4 wn = pl.block(b + 1);
+        batch(w.x, w.y);
+        batch(w.z, w.w);
+        w = wn;
+    }
+    (void)bl;
+}
+
+/*! @brief loader of a block-union kernel: staged blocks read the LDS union, the others gather per lane (the loop of
+ *         the production kernels, forEachNeighborDirect) */
+template<class R, int NG, int UCAP>
+struct BlockUnionLoader
+{
+    using Shared = BlockUnionShared<NG, UCAP, int(sizeof(R) / 16)>;
+    const R* r;
+    const Shared* sh;
+    const BlockLane* bl;
+    bool staged; // block-uniform
+
+    __device__ R operator()(unsigned j) const { return r[j]; }
+};
+
+template<int B, class R, int NG, int UCAP, class F>
+__device__ void forEachNeighbor(const PackedLane* pl, int, unsigned, const BlockUnionLoader<R, NG, UCAP>& ld, F&& f)
+{
+    if (ld.staged) forEachNeighborUnion<R, NG, UCAP>(*pl, *ld.bl, *ld.sh, f);
+    else forEachNeighborDirect(*pl, ld, f);
 }
 
 } // namespace sphx::hip

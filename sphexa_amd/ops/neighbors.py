@@ -227,7 +227,7 @@ def _pool_plan(prev: NeighborList | None, groups: int, ng0: int, stripes: int):
     ~1.3 ng0 at shell steps)"""
     if prev is not None and prev.grouped and prev.plan is not None and prev.plan[0] == groups:
         return prev.plan[1], prev.plan[2]
-    masks = 1 if _lib.hip().staged_mask() else 0
+    masks = 1 if _lib.hip().list_masks_wanted() else 0
     return max(1, round(ng0 / 8) + 1 + masks), max(8, -(-int(0.35 * ng0 / 8 * groups + 0.5) // stripes))
 
 
