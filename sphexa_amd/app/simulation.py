@@ -4,6 +4,9 @@
     sim.run(steps=10)        # or sim.step() in a loop
     sim.d["rho"], sim.domain.start_index(), ...
 
+``ewald=S`` (S > 0) makes the self-gravity of a fully periodic cubic box periodic: S shells of replicas are walked
+explicitly and every farther image comes from the Ewald sum of the root multipole (single rank).
+
 Parity: reference main/src/sphexa/sphexa.cpp:104-200 (initializer -> propagator -> domain -> sync -> time loop).
 The global bucket size follows the reference: max(bucketSizeFocus, N / (100 * numRanks)).
 """
@@ -25,10 +28,27 @@ from ..parallel.domain import Domain
 from ..ops import _lib
 
 
+def check_ewald(shells: int, G: float, box, num_ranks: int):
+    """the conditions of periodic (Ewald) self-gravity; raises ValueError when one does not hold"""
+    from ..utils.box import PERIODIC
+
+    if shells < 0:
+        raise ValueError("Ewald gravity: the number of replica shells must not be negative")
+    if G == 0.0:
+        raise ValueError("Ewald gravity needs a non-zero gravitational constant (G)")
+    if any(b != PERIODIC for b in box.bc):
+        raise ValueError("Ewald gravity needs a box that is periodic in all three directions")
+    L = box.hi[0] - box.lo[0]
+    if any(abs((box.hi[k] - box.lo[k]) - L) > 1e-12 * L for k in range(3)):
+        raise ValueError("Ewald gravity needs a cubic box")
+    if num_ranks > 1:
+        raise ValueError("Ewald gravity runs on a single rank only")
+
+
 class Simulation:
     def __init__(self, init: str, n: int = 50, prop: str = "ve", device=None, glass=None, av_clean=False,
                  comm: Comm | None = None, theta: float | None = None, G: float | None = None, out=None,
-                 quiet=True, bucket_size_focus: int | None = None, initializer=None):
+                 quiet=True, bucket_size_focus: int | None = None, initializer=None, ewald: int = 0):
         self.comm = comm or Comm()
         rank, size = self.comm.rank, self.comm.size
         if device is None:
@@ -46,6 +66,9 @@ class Simulation:
             self.d.g = float(G)
         if theta is None:
             theta = 0.5 if self.d.g != 0.0 else 1.0
+        if ewald:
+            check_ewald(int(ewald), self.d.g, box, size)
+            self.propagator.ewald_shells = int(ewald)
         # (tuning: SPHX_BUCKET_FOCUS overrides the local octree's leaf capacity, reference bucketSizeFocus = 64)
         # (an explicit argument wins over the environment)
         if bucket_size_focus is None:

@@ -39,6 +39,9 @@ Where possible options are:
     --glass FILE        Use glass block as template to generate initial x,y,z configuration (built-in otherwise)
     --theta NUM         Gravity accuracy parameter [default 0.5 when self-gravity is active]
     --G NUM             Gravitational constant [default dependent on test case]
+    --ewald [S]         Periodic self-gravity (fully periodic cubic box, one rank): S shells of replicas walked
+                        explicitly [1], farther images by Ewald summation. A run option: not stored in snapshots,
+                        give it again when restarting from a file
     --prop STRING       Choice of SPH propagator [default: modern SPH]. For standard SPH, use "std"
     -s NUM              NUM Number of iterations (time-steps) [200] or simulation time if NUM is not integral
     -w NUM              Dump particle data every NUM iterations (time-steps) [-1]
@@ -126,6 +129,12 @@ def main(argv=None) -> int:
         d.g = float(parser.get("--G", 0.0))
     have_grav = d.g != 0.0
     theta = float(parser.get("--theta", 0.5 if have_grav else 1.0))
+    if parser.exists("--ewald"):
+        from .simulation import check_ewald
+
+        shells = int(parser.get("--ewald", 1))
+        check_ewald(shells, d.g, box, num_ranks)
+        propagator.ewald_shells = shells
 
     if not parser.exists("-o"):
         out_file += writer.suffix

@@ -540,6 +540,20 @@ PYBIND11_MODULE(_sphx_hip, m)
                                       P<double>(z), P<float>(h), P<float>(mm), G, P<float>(ax), P<float>(ay),
                                       P<float>(az), P<double>(ugrav), P<double>(esum), P<int>(overflow), St(s));
           });
+    // ------------------------------------------------------------------------- periodic self-gravity (Ewald)
+    m.def("compute_gravity_ewald",
+          [](int64_t first, int64_t last, Ptr child, Ptr n2l, Ptr ns, Ptr ne, Ptr centers, Ptr mp, Ptr x, Ptr y,
+             Ptr z, Ptr h, Ptr mm, double G, double L, int shells, Ptr ktable, Ptr sums, Ptr ax, Ptr ay, Ptr az,
+             Ptr ugrav, Ptr esum, Ptr overflow, Ptr s)
+          {
+              computeGravityEwald(first, last, P<int32_t>(child), P<int32_t>(n2l), P<int32_t>(ns), P<int32_t>(ne),
+                                  P<double>(centers), P<void>(mp), P<double>(x), P<double>(y), P<double>(z),
+                                  P<float>(h), P<float>(mm), G, L, shells, P<double>(ktable), P<double>(sums),
+                                  P<float>(ax), P<float>(ay), P<float>(az), P<double>(ugrav), P<double>(esum),
+                                  P<int>(overflow), St(s));
+          });
+    m.def("ewald_ktable", [](double L) { return ewaldKTableHost(L); },
+          "k-space coefficient table of a cubic box of length L (sphx/ewald.hpp ewaldKTable)");
     // ---------------------------------------------------------------------------------------------- cooling
     m.def("cool_particles", [](int64_t first, int64_t last, double dt, Ptr rho, Ptr u, Ptr du,
                                const std::array<double, 7>& a, Ptr s)

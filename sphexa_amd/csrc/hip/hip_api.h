@@ -289,6 +289,15 @@ void computeGravityMultipole(int order, int64_t first, int64_t last, const int32
                              double G, float* ax, float* ay, float* az, double* ugrav, double* esum, int* overflow,
                              hipStream_t s);
 
+// ewald.hip (periodic self-gravity of a cubic box; math: sphx/ewald.hpp)
+//! ktable: ewaldKTableHost(L) copied to the device; sums: 4 (last - first) doubles of scratch
+void computeGravityEwald(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
+                         const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
+                         const double* z, const float* h, const float* m, double G, double L, int numShells,
+                         const double* ktable, double* sums, float* ax, float* ay, float* az, double* ugrav,
+                         double* esum, int* overflow, hipStream_t s);
+std::vector<double> ewaldKTableHost(double L);
+
 // gravity.hip
 void gravityUpsweepFused(const int32_t* n2l, int64_t N, const int32_t* ns, const int32_t* ne, const double* x,
                          const double* y, const double* z, const float* m, const int32_t* child,

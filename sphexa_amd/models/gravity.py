@@ -89,6 +89,19 @@ class MultipoleHolder:
         if not self.pending:
             self._finalize(d, [])
 
+    def traverse_ewald(self, d, domain, shells: int):
+        """periodic self-gravity of a cubic box (ops.gravity.compute_gravity_ewald: ``shells`` of replicas walked
+        explicitly, the farther images through the Ewald sum of the root multipole), single rank. The energy comes
+        to the host with the call: nothing stays pending"""
+        self.finish_sync(d)
+        self._rstats = None
+        self.pending = []
+        self._host_energy = G.compute_gravity_ewald(domain.octree, self.centers, self.multipoles,
+                                                    domain.start_index(), domain.end_index(), d["x"], d["y"], d["z"],
+                                                    d["h"], d["m"], d.g, domain.box, d["ax"], d["ay"], d["az"],
+                                                    shells=shells)
+        self._finalize(d, [])
+
     def finish(self, d, host_vals):
         """host values of ``pending`` (one list per pending evaluation, in order)"""
         energies = [p.finish(v) for p, v in zip(self.pending, host_vals)]

@@ -61,6 +61,9 @@ class Propagator:
     defer_host = False
     # propagators that use the new dt on the host within the step (stirring, cooling) never defer
     needs_host_dt = False
+    # periodic self-gravity: > 0 evaluates gravity with this many shells of explicit replicas plus the Ewald lattice
+    # sum (MultipoleHolder.traverse_ewald) on the plain path of _gravity: no side streams, no deferred energy
+    ewald_shells = 0
 
     def __init__(self, out=sys.stdout, rank: int = 0, quiet: bool = False):
         self.out = out if rank == 0 and not quiet else None
@@ -135,6 +138,8 @@ class Propagator:
         the search (the fork point is recorded here, before the search)"""
         if d.g == 0.0 or d.device.type != "cuda" or not GRAVITY_OVERLAP or not GRAVITY_PREPARE:
             return None
+        if self.ewald_shells > 0:
+            return None
         fork = torch.cuda.Event()
         fork.record(torch.cuda.current_stream(d.device))
         return lambda: self._gravity_prepare_launch(domain, d, fork)
@@ -171,6 +176,8 @@ class Propagator:
         loop. Returns None (gravity runs in _gravity as before) without gravity, on the CPU or with
         SPHX_GRAV_OVERLAP=0."""
         if d.g == 0.0 or d.device.type != "cuda" or not GRAVITY_OVERLAP:
+            return None
+        if self.ewald_shells > 0:
             return None
         from ..ops.reduce import zero_
 
@@ -242,7 +249,10 @@ class Propagator:
                 self.gravity = MultipoleHolder()
             self.gravity.upsweep(d, domain)
             self.timer.step("Upsweep")
-            self.gravity.traverse(d, domain)
+            if self.ewald_shells > 0:
+                self.gravity.traverse_ewald(d, domain, self.ewald_shells)
+            else:
+                self.gravity.traverse(d, domain)
             self.timer.step("Gravity")
 
     def compute_timestep(self, domain, d, *extra):

@@ -514,28 +514,49 @@ def m2p_flat(first: int, last: int, x, y, z, m, mcenters: torch.Tensor, mquads: 
                                      az.data_ptr(), 0 if ugrav is None else ugrav.data_ptr()))
 
 
+# k-space coefficient tables of the GPU Ewald sum: one per (box length, device), computed by the host in fp64
+# (csrc/include/sphx/ewald.hpp ewaldKTable)
+_EWALD_KTABLES: dict = {}
+
+
+def _ewald_ktable(L: float, device) -> torch.Tensor:
+    key = (float(L), str(device))
+    t = _EWALD_KTABLES.get(key)
+    if t is None:
+        if len(_EWALD_KTABLES) >= 8:
+            _EWALD_KTABLES.clear()
+        t = _EWALD_KTABLES[key] = torch.tensor(_lib.hip().ewald_ktable(float(L)), dtype=torch.float64).to(device)
+    return t
+
+
 def compute_gravity_ewald(tree: Octree, centers, mp, first: int, last: int, x, y, z, h, m, G: float, box: Box,
                           ax, ay, az, shells: int = 1, ugrav=None) -> float:
     """periodic self-gravity (cubic box): Barnes-Hut over the central box and ``shells`` of replicas plus the Ewald
     lattice sum of the root multipole for all farther images (reference nbody/traversal_ewald_cpu.hpp, CPU-only
-    there as well). Device tensors are evaluated through host copies. Adds G * a to ax, ay, az."""
+    there). Adds G * a to ax, ay, az for targets [first, last) and the per-particle energy to ``ugrav``; returns
+    0.5 * sum G m phi. Device tensors: csrc/hip/ewald.hip on the current stream (one host copy: the energy and the
+    overflow flag)."""
     L = box.hi[0] - box.lo[0]
     if any(abs((box.hi[d] - box.lo[d]) - L) > 1e-12 * L for d in range(3)):
         raise ValueError("Ewald gravity needs a cubic box")
-    dev = x.device
-    host = [t.cpu() if t is not None else None for t in (x, y, z, h, m, ax, ay, az, ugrav)]
-    hx, hy, hz, hh, hm, hax, hay, haz, hu = host
-    args = [tree.child_offsets.cpu(), tree.node_to_leaf.cpu(), tree.node_start.cpu(), tree.node_end.cpu(),
-            centers.cpu(), mp.cpu()]
-    e = _lib.cpu().compute_gravity_ewald(first, last, *[a.data_ptr() for a in args], hx.data_ptr(), hy.data_ptr(),
-                                         hz.data_ptr(), hh.data_ptr(), hm.data_ptr(), float(G), float(L), int(shells),
-                                         hax.data_ptr(), hay.data_ptr(), haz.data_ptr(),
-                                         0 if hu is None else hu.data_ptr())
-    if dev.type != "cpu":
-        for dst, src in ((ax, hax), (ay, hay), (az, haz), (ugrav, hu)):
-            if dst is not None:
-                dst.copy_(src)
-    return float(e)
+    if last <= first:
+        return 0.0
+    args = (tree.child_offsets.data_ptr(), tree.node_to_leaf.data_ptr(), tree.node_start.data_ptr(),
+            tree.node_end.data_ptr(), centers.data_ptr(), mp.data_ptr(), x.data_ptr(), y.data_ptr(), z.data_ptr(),
+            h.data_ptr(), m.data_ptr(), float(G), float(L), int(shells))
+    out = (ax.data_ptr(), ay.data_ptr(), az.data_ptr(), 0 if ugrav is None else ugrav.data_ptr())
+    if x.is_cuda:
+        ktable = _ewald_ktable(L, x.device)
+        sums = torch.empty(4 * (last - first), dtype=torch.float64, device=x.device)
+        # [energy (float64), overflow count (as an int32 in the second word)]: one fill, one copy to the host
+        res = zero_(torch.empty(2, dtype=torch.float64, device=x.device))
+        _lib.hip().compute_gravity_ewald(first, last, *args, ktable.data_ptr(), sums.data_ptr(), *out,
+                                         res.data_ptr(), res[1:].data_ptr(), _stream())
+        host = res.cpu()
+        if int(host.view(torch.int32)[2]) != 0:
+            raise RuntimeError("Ewald traversal stack overflow")
+        return float(host[0])
+    return float(_lib.cpu().compute_gravity_ewald(first, last, *args, *out))
 
 
 def direct_ewald(x, y, z, m, G: float, L: float):
