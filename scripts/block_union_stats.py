@@ -2,7 +2,7 @@
 """Source unions of blocks of SFC-consecutive target groups, from the slot masks of the packed GPU neighbor lists
 (design data of the block-union staged pair loops, csrc/hip/staged.h).
 
-For a sample of blocks of 4 and 8 groups: the merged chunk slots (distinct chunk bases), the records of the merged
+For a sample of blocks of 4, 8 and 16 groups (16: the 1024-thread blocks of the XMass and Gradh loops): the merged chunk slots (distinct chunk bases), the records of the merged
 masks (what a block stages in LDS), the groups' slot counts, and the share of blocks that fit a capacity.
 
   python scripts/block_union_stats.py --init sedov -n 200 --caps 1128,2264
@@ -53,7 +53,7 @@ def main():
     caps = [int(c) for c in args.caps.split(",")]
     s = torch.arange(64, device=dev)
     bit = torch.arange(32, device=dev)
-    for ng in (4, 8):
+    for ng in (4, 8, 16):
         nb = G // ng
         k = min(args.sample_blocks, nb)
         b0 = (nb - k) // 2

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Share of blocks that the block-union staged IAD and AV loops (csrc/hip/staged.h) stage in LDS or hand to the gathered
-loop, counted by the kernels themselves over a few steps of a case.
+"""Share of blocks that the block-union staged loops (csrc/hip/staged.h; --mask 66 = XMass and Gradh, 12 = IAD and AV,
++ 32 in 256-thread runs) stage in LDS or hand to the gathered loop, counted by the kernels themselves over a few steps
+of a case.
 
   python scripts/staged_block_share.py --init sedov -n 400 [--mask 44]
 """

@@ -173,27 +173,30 @@ static const unsigned kPairMask = []
 void setPairBlock(int block) { g_pairBlock = block == 512 ? 512 : kBlock; }
 
 /* Loops that run LDS-staged (staged.h), fixed-point path only: bit 0 XMass (one group per workgroup, W waves; slower
- * than the gathered loop, kept for A/B), bit 2 IAD and bit 3 the AV switches (block-union staging: the source union of
- * the block's 8 or 4 groups in LDS, one wave per group, results bit-identical to the gathered loops). Bits 1 (Gradh)
- * and 4 (momentum) have no staged loop: those loops gather. Bit 5: bits 2 and 3 also in runs on 256-thread blocks
- * (setPairBlock: self-gravity); without it such runs gather, since the union of 4 groups (~1300 records on a lattice,
- * ~1700 on a glass) does not fit the LDS of four blocks per CU (profiles/r7/staged_block/README.md).
- * Default: IAD and AV (Sedov -n 400: IAD 15.4 -> 11.5 ms, AV 13.3 -> 9.4 ms). SPHX_STAGED overrides the default;
- * setStaged (tests, A/B) at run time. */
+ * than the gathered loop, kept for A/B), bit 1 Gradh, bit 2 IAD, bit 3 the AV switches and bit 6 XMass (block-union
+ * staging: the source union of the block's groups in LDS, one wave per group, results bit-identical to the gathered
+ * loops; bit 6 wins over bit 0). Bit 4 (momentum) has no staged loop: it gathers. Bit 5: the block-union loops also in
+ * runs on 256-thread blocks (setPairBlock: self-gravity); without it such runs gather: the union of 4 groups (~1300
+ * records on a lattice, ~1700 on a glass) does not fit the LDS of four blocks per CU with the 32-B records of IAD and AV
+ * (profiles/r7/staged_block/README.md); with the 16-B records of XMass and Gradh it fits, at half the gathered loops'
+ * occupancy (profiles/r8/staged_xg/README.md).
+ * Default: the four block-union loops, 78 (Sedov -n 400: IAD 15.4 -> 11.5 ms, AV 13.3 -> 9.4 ms, XMass 7.8 -> 6.5 ms,
+ * Gradh 8.5 -> 7.8 ms). SPHX_STAGED overrides the default; setStaged (tests, A/B) at run time. */
 static unsigned g_staged = []
 {
     const char* e = std::getenv("SPHX_STAGED");
-    return e ? unsigned(std::strtoul(e, nullptr, 0)) : 12u;
+    return e ? unsigned(std::strtoul(e, nullptr, 0)) : 78u;
 }();
 
 void setStaged(unsigned mask) { g_staged = mask; }
 unsigned stagedMask() { return g_staged; }
 
-//! whether loop `loop` (2 IAD, 3 AV) runs its block-union kernel in this run
+//! whether loop `loop` (0 XMass, 1 Gradh, 2 IAD, 3 AV) runs its block-union kernel in this run
 static bool unionLoopOn(int loop)
 {
-    const bool big = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
-    return ((g_staged >> loop) & 1u) && (big || (g_staged & 32u));
+    const bool big     = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
+    const unsigned bit = loop == 0 ? 6u : unsigned(loop); // (bit 0 is the per-group staged XMass)
+    return ((g_staged >> bit) & 1u) && (big || (g_staged & 32u));
 }
 
 // tests: blocks staged / fallen back by the block-union loops (one atomic per block); null in production
@@ -214,12 +217,53 @@ static_assert(sizeof(BlockUnionShared<8, kUnionCap<512>, 2>) * 2 <= 160 * 1024 &
                   sizeof(BlockUnionShared<4, kUnionCap<256>, 2>) * 4 <= 160 * 1024,
               "16 waves per CU with the unions in LDS");
 
+// XMass and Gradh (16-B records), shapes of the block-union loops: 16 groups per 1024-thread block (the gathered loops'
+// block: two blocks per CU, 8 waves per SIMD), 8 groups per 512-thread block (three blocks per CU, 6 waves per SIMD)
+// and, in 256-thread runs, 4 groups per block (four blocks per CU). Capacities: what the LDS share leaves after the
+// tables. SPHX_STB_XG_BLOCK (build default, environment at start-up: A/B) picks 1024 or 512 for the 512-thread runs.
+#ifndef SPHX_STB_XG_U1024
+#define SPHX_STB_XG_U1024 3900
+#endif
+#ifndef SPHX_STB_XG_U512
+#define SPHX_STB_XG_U512 2704
+#endif
+#ifndef SPHX_STB_XG_U256
+#define SPHX_STB_XG_U256 2260
+#endif
+#ifndef SPHX_STB_XG_BLOCK
+#define SPHX_STB_XG_BLOCK 1024
+#endif
+template<int B>
+constexpr int kUnionCapXg = B == 1024 ? SPHX_STB_XG_U1024 : B == 512 ? SPHX_STB_XG_U512 : SPHX_STB_XG_U256;
+static_assert(sizeof(BlockUnionShared<16, kUnionCapXg<1024>, 1>) * 2 <= 160 * 1024 &&
+                  sizeof(BlockUnionShared<8, kUnionCapXg<512>, 1>) * 3 <= 160 * 1024 &&
+                  sizeof(BlockUnionShared<4, kUnionCapXg<256>, 1>) * 4 <= 160 * 1024,
+              "blocks per CU with the 16-B unions in LDS");
+static const int kXgBlock = []
+{
+    const char* e = std::getenv("SPHX_STB_XG_BLOCK");
+    return (e ? std::atoi(e) : SPHX_STB_XG_BLOCK) == 512 ? 512 : 1024;
+}();
+
+//! @brief f(std::integral_constant<int, B>) with the block size of the block-union XMass / Gradh loop of this run
+template<class F>
+inline void withXgBlock(F&& f, int loop)
+{
+    const bool big = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
+    if (!big) f(std::integral_constant<int, kBlock>{});
+    else if (kXgBlock == 512) f(std::integral_constant<int, 512>{});
+    else f(std::integral_constant<int, 1024>{});
+}
+
 // tests: the search stores the slot masks even when no staged loop runs (packed-list format checks)
 static bool g_listMasks = false;
 void setListMasks(bool on) { g_listMasks = on; }
 bool listMasksForced() { return g_listMasks; }
 // the search stores the slot masks (16 B per particle) only while a loop of this run reads them
-bool listMasksWanted() { return g_listMasks || (g_staged & 1u) || unionLoopOn(2) || unionLoopOn(3); }
+bool listMasksWanted()
+{
+    return g_listMasks || (g_staged & 1u) || unionLoopOn(0) || unionLoopOn(1) || unionLoopOn(2) || unionLoopOn(3);
+}
 
 //! grid of a staged loop: one workgroup per target group
 inline unsigned gridStaged(const NbrArgs& a) { return unsigned((a.last - a.first + 63) / 64); }
@@ -601,6 +645,44 @@ __global__ __launch_bounds__(64 * W) void xmassQStagedKernel(NbrArgs a, SphConst
     if (xmOut) xmOut[i] = SrcXmQ{pi.x, pi.y, pi.z, v};
 }
 
+/*! @brief xmassQKernel with the block's SrcPosQ union staged in LDS (staged.h, block-union staging: one wave per
+ *         group, a block whose union does not fit runs the gathered loop). Same sum in the same order. */
+// (the 1024-thread shape needs 8 waves per SIMD, i.e. at most 64 VGPRs, for its two blocks per CU)
+template<int B, int kKf, int UCAP>
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(B == 1024 ? 8 : 4))) void xmassQUnionKernel(
+    NbrArgs a, SphConsts sc, QFrame q, const float* __restrict__ h, const SrcPosQ* __restrict__ rec,
+    const float* __restrict__ wh, float* __restrict__ xm, SrcXmQ* __restrict__ xmOut, unsigned* counters)
+{
+    using Ld = BlockUnionLoader<SrcPosQ, B / 64, UCAP>;
+    __shared__ typename Ld::Shared sh;
+    int64_t i;
+    PackedLane pl;
+    BlockLane bl;
+    unsigned n;
+    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
+    const bool staged = stageBlockUnion<SrcPosQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
+    if (!staged) loadChunkTable(bl, pl, sh);
+    const Ld ld{rec, &sh, &bl, staged};
+    const SrcPosQ pi = ld(unsigned(i));
+    const float hi = h[i], hInv = 1.f / hi, h3Inv = hInv * hInv * hInv;
+    const float sx = q.inv[0] * 0.25f * hInv, sy = q.inv[1] * 0.25f * hInv, sz = q.inv[2] * 0.25f * hInv;
+    float rho0 = 0.f;
+    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
+        float sum = 0.f;
+        forEachNeighbor<SPHX_BATCH_POS>(&pl, 0, n, ld, [&](unsigned, const SrcPosQ& pj) {
+            const float ux = float(int32_t(pi.x - pj.x)) * sx;
+            const float uy = float(int32_t(pi.y - pj.y)) * sy;
+            const float uz = float(int32_t(pi.z - pj.z)) * sz;
+            sum += kf.wqIn(sqrtF(ux * ux + uy * uy + uz * uz)) * pj.m;
+        });
+        rho0 = pi.m + sum / kf.wqScale();
+    });
+    if (!valid) return;
+    const float v = pi.m / (rho0 * float(sc.K) * h3Inv);
+    xm[i]         = v;
+    if (xmOut) xmOut[i] = SrcXmQ{pi.x, pi.y, pi.z, v}; // Gradh's record of this target
+}
+
 // staged shapes (waves per group, union capacity in records), per loop
 #ifndef SPHX_ST_XMASS_W
 #define SPHX_ST_XMASS_W 4
@@ -616,24 +698,14 @@ struct EosOut
     float *prho = nullptr, *c = nullptr, *rho = nullptr, *p = nullptr;
 };
 
-template<class R, class G, int B = kBlock, int kKf = 0>
-__global__ __launch_bounds__(B) void veDefGradhKernel(NbrArgs a, SphConsts sc, G box,
-                                                           const float* __restrict__ h, const R* __restrict__ rec,
-                                                           const float* __restrict__ wh, const float* __restrict__ whd,
-                                                           float* __restrict__ kx, float* __restrict__ gradh,
-                                                           float mUniform, const float* __restrict__ vx,
-                                                           const float* __restrict__ vy, const float* __restrict__ vz,
-                                                           SrcIadQ* __restrict__ iadOut, EosOut eos = EosOut{})
+//! @brief what the Gradh loops store for target i: kx, gradh, the IAD loop's record and the fused equation of state
+template<class R>
+__device__ __forceinline__ void gradhEpilogue(int64_t i, const SphConsts& sc, const R* __restrict__ rec, float k,
+                                              float g, float* __restrict__ kx, float* __restrict__ gradh,
+                                              float mUniform, const float* __restrict__ vx,
+                                              const float* __restrict__ vy, const float* __restrict__ vz,
+                                              SrcIadQ* __restrict__ iadOut, const EosOut& eos)
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
-    int64_t i;
-    PackedLane pl;
-    unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
-    float k, g;
-    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
-                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], coopOf(rec, tile, i, a), kf, k, g, mUniform); });
-    if (!valid) return;
     kx[i]    = k;
     gradh[i] = g;
     if constexpr (std::is_same_v<R, SrcXmQ>)
@@ -657,6 +729,53 @@ __global__ __launch_bounds__(B) void veDefGradhKernel(NbrArgs a, SphConsts sc, G
             if (eos.p) eos.p[i] = float(pi);
         }
     }
+}
+
+template<class R, class G, int B = kBlock, int kKf = 0>
+__global__ __launch_bounds__(B) void veDefGradhKernel(NbrArgs a, SphConsts sc, G box,
+                                                           const float* __restrict__ h, const R* __restrict__ rec,
+                                                           const float* __restrict__ wh, const float* __restrict__ whd,
+                                                           float* __restrict__ kx, float* __restrict__ gradh,
+                                                           float mUniform, const float* __restrict__ vx,
+                                                           const float* __restrict__ vy, const float* __restrict__ vz,
+                                                           SrcIadQ* __restrict__ iadOut, EosOut eos = EosOut{})
+{
+    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
+    int64_t i;
+    PackedLane pl;
+    unsigned n;
+    const bool valid = targetOf<B>(a, i, pl, n);
+    float k, g;
+    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
+                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], coopOf(rec, tile, i, a), kf, k, g, mUniform); });
+    if (!valid) return;
+    gradhEpilogue(i, sc, rec, k, g, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
+}
+
+/*! @brief veDefGradhKernel on SrcXmQ records with the block's source union staged in LDS (staged.h, block-union
+ *         staging; a block whose union does not fit runs the gathered loop). Same sums in the same order, the same
+ *         fused epilogue. */
+template<int B, int kKf, int UCAP>
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(B == 1024 ? 8 : 4))) void veDefGradhUnionKernel(
+    NbrArgs a, SphConsts sc, QFrame box, const float* __restrict__ h, const SrcXmQ* __restrict__ rec,
+    const float* __restrict__ wh, const float* __restrict__ whd, float* __restrict__ kx, float* __restrict__ gradh,
+    float mUniform, const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
+    SrcIadQ* __restrict__ iadOut, EosOut eos, unsigned* counters)
+{
+    using Ld = BlockUnionLoader<SrcXmQ, B / 64, UCAP>;
+    __shared__ typename Ld::Shared sh;
+    int64_t i;
+    PackedLane pl;
+    BlockLane bl;
+    unsigned n;
+    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
+    const bool staged = stageBlockUnion<SrcXmQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
+    if (!staged) loadChunkTable(bl, pl, sh);
+    float k, g;
+    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
+                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], Ld{rec, &sh, &bl, staged}, kf, k, g, mUniform); });
+    if (!valid) return;
+    gradhEpilogue(i, sc, rec, k, g, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
 }
 
 __global__ void eosVeKernel(int64_t first, int64_t last, SphConsts sc, const double* __restrict__ temp,
@@ -1431,6 +1550,21 @@ void xmass(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t ntot, 
         const QFrame q = qframeOf(box, sc.fixedPoint);
         packRanges(inDone, a, ntot, [&](int64_t lo, int64_t hi)
                    { packPosQKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, m, q, (SrcPosQ*)rec); });
+        if (unionLoopOn(0))
+        {
+            withXgBlock([&](auto bc)
+                        {
+                            constexpr int B = decltype(bc)::value;
+                            withKf(sc, [&](auto kk)
+                                   {
+                                       xmassQUnionKernel<B, decltype(kk)::value, kUnionCapXg<B>>
+                                           <<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcPosQ*)rec, wh,
+                                                                      xm, (SrcXmQ*)xmOut, g_stagedCounters);
+                                   });
+                        }, 0);
+            SPHX_LAUNCH_CHECK();
+            return;
+        }
         if (g_staged & 1u)
         {
             xmassQStagedKernel<SPHX_ST_XMASS_W, SPHX_ST_XMASS_U><<<gridStaged(a), 64 * SPHX_ST_XMASS_W, 0, s>>>(
@@ -1464,6 +1598,25 @@ void veDefGradh(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t n
         const QFrame q = qframeOf(box, sc.fixedPoint);
         packRanges(inDone, a, ntot, [&](int64_t lo, int64_t hi)
                    { packXmQKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, xm, q, (SrcXmQ*)rec); });
+        if (unionLoopOn(1))
+        {
+            withXgBlock([&](auto bc)
+                        {
+                            withKf(sc, [&](auto kk)
+                                   {
+                                       // (the runtime kernel function needs 66 VGPRs: 7 waves per SIMD, which is one
+                                       // 1024-thread block per CU; it takes the 512-thread shape)
+                                       constexpr int KK = decltype(kk)::value, B0 = decltype(bc)::value;
+                                       constexpr int B  = KK == 0 && B0 == 1024 ? 512 : B0;
+                                       veDefGradhUnionKernel<B, KK, kUnionCapXg<B>>
+                                           <<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcXmQ*)rec, wh,
+                                                                      whd, kx, gradh, mUniform, vx, vy, vz,
+                                                                      (SrcIadQ*)iadOut, eos, g_stagedCounters);
+                                   });
+                        }, 1);
+            SPHX_LAUNCH_CHECK();
+            return;
+        }
         withPairBlockL<SPHX_GRADH_BLOCK>([&](auto bc)
                       {
                           constexpr int B = decltype(bc)::value;

@@ -1,7 +1,7 @@
 /*! LDS-staged SPH pair loops (gfx950): the sources of a 64-target group are copied into LDS once per group and every
  *  neighbor step reads its record there instead of gathering it from L2. Two designs: one workgroup per group (below;
- *  XMass, slower than gathering, kept for A/B) and, in the second half of this file, the union of a block's 4 or 8
- *  groups staged once per block with one wave per group (IAD and AV: the production loops).
+ *  XMass, slower than gathering, kept for A/B) and, in the second half of this file, the union of a block's 4, 8 or 16
+ *  groups staged once per block with one wave per group (XMass, Gradh, IAD and AV: the production loops).
  *
  * Parity: the loops themselves are the reference's hydro_ve kernels (sph/include/sph/hydro_ve/*_kern.hpp, e.g.
  * momentum_energy_kern.hpp:113-222), here through the shared J-loops of sphx/sph_math.hpp. What differs is where
@@ -394,14 +394,18 @@ __device__ void reduceAcrossMax(const StagedLoader<R, W, UCAP, kSide>& ld, T&...
  *    2. one thread per hash entry: popcount of the merged mask, block-wide prefix sum -> the entry's first record
  *       position; the non-empty entries are listed densely;
  *    3. every lane looks its slot's merged entry up and keeps {c0, base, mask} in registers; the waves copy the
- *       records of the dense entries (lane k = particle c0 + k: coalesced) to their positions;
- *    4. the hash is dead: its memory becomes the per-wave slot tables (one 16-B entry per slot).
- *  Neighbor step: code (slot, off) -> table entry (one ds_read_b128) -> position base + popcount(mask below off)
- *  -> record (RC x ds_read_b128). The index c0 + off serves the self test only. Slot 0 (padding codes: the target
- *  itself) has the entry {group's first particle, 0, 0}: it decodes to the target and is skipped like it.
+ *       records of the dense entries (lane k = particle c0 + k: coalesced) to their positions; every lane finds the
+ *       record of its own target (the one or two slots of its wave that overlap the group's particles);
+ *    4. the hash is dead: its memory becomes the per-wave slot tables, one 16-B entry per slot: for each half of the
+ *       slot's 64 sources the byte offset of its first record and its 32-bit mask.
+ *  Neighbor step: code (slot, off) -> table entry (one ds_read_b128) -> the half of off -> record offset = the half's
+ *  offset + record size x popcount(mask below off) -> record (RC x ds_read_b128): 11 VALU instructions, no source
+ *  index. The target's own entry is the one whose offset equals the target's; slot 0 (padding codes) has the entry
+ *  {spare, 0, spare, 0} and decodes to the spare record past the capacity, which is skipped too.
  *  A block falls back, as a whole, to the gathered loop in the same kernel when the merged union exceeds UCAP records,
  *  a group has more than kBuSlots slots, the lists were searched without slot masks (T == Tc), a table value is out of
- *  range or the hash is full. The chunk tables of the gathered loop share the records' LDS. */
+ *  range, the hash is full or a target is staged under two slots. The chunk tables of the gathered loop share the
+ *  records' LDS. */
 constexpr unsigned kBuSlots = 64;
 constexpr uint32_t kBuEmpty = 0xFFFFFFFFu;
 
@@ -412,6 +416,7 @@ struct BlockLane
     const int32_t* rowsInt; // row pool
     unsigned nch, Tc, T;    // chunk slots (0: no group), chunk-base rows, table rows
     unsigned gfirst;        // first particle of the group
+    unsigned selfAddr;      // staged blocks: byte offset of this lane's own target in the LDS records (stageBlockUnion)
 
     __device__ __forceinline__ int32_t rowOf(unsigned o) const
     {
@@ -449,6 +454,7 @@ __device__ __forceinline__ bool blockTargetOf(const NbrArgs& a, int64_t& i, Pack
     bl.rowsInt          = a.nidx + packedTableRegion(G, a.ngmax);
     bl.nch = bl.Tc = bl.T = 0;
     bl.gfirst             = unsigned(a.first + g * 64);
+    bl.selfAddr           = 0;
     pl.nblk               = 0;
     if (g < G) // wave-uniform: waves past the last group have no table
     {
@@ -466,6 +472,11 @@ __device__ __forceinline__ bool blockTargetOf(const NbrArgs& a, int64_t& i, Pack
     SPHX_DCHECK(pl.nblk <= listBlocksMax(a.ngmax), 1);
     pl.nblk = min(pl.nblk, listBlocksMax(a.ngmax));
 #endif
+    // A group without list blocks has no slots. Every searched group has at least its targets' own entries, so
+    // nblk == 0 means that the search ran out of list rows for this group (neighbors.hip, rowsLost): its row ordinals
+    // then point at row 0, another group's data, and a loop enqueued before the host repeats the search
+    // (models/propagators.py) must neither stage nor decode it.
+    if (pl.nblk == 0) bl.nch = 0;
     if (i >= a.last)
     {
         i       = a.last - 1;
@@ -494,7 +505,7 @@ __device__ __forceinline__ void loadChunkTable(const BlockLane& bl, PackedLane& 
 /*! @brief the prologue (file comment above; all threads of the block call it): true if the block's union is staged
  *         (block-uniform), false if the block takes the gathered loop (nothing of sh is in use then) */
 template<class R, int NG, int UCAP>
-__device__ bool stageBlockUnion(const BlockLane& bl, const R* __restrict__ rec, unsigned ntot,
+__device__ bool stageBlockUnion(BlockLane& bl, const R* __restrict__ rec, unsigned ntot,
                                 BlockUnionShared<NG, UCAP, int(sizeof(R) / 16)>& sh, unsigned* counters)
 {
     constexpr int RC = int(sizeof(R) / 16);
@@ -568,10 +579,10 @@ __device__ bool stageBlockUnion(const BlockLane& bl, const R* __restrict__ rec, 
     }
     const unsigned excl = before + incl - pk;
     const unsigned nrec = total & 0xFFFFu, nent = total >> 16;
-    const bool staged   = sh.fail == 0u && nrec <= unsigned(UCAP);
-    if (counters && t == 0) atomicAdd(&counters[staged ? 0 : 1], 1u);
-    if (!staged)
+    const bool fits     = sh.fail == 0u && nrec <= unsigned(UCAP);
+    if (!fits)
     {
+        if (counters && t == 0) atomicAdd(&counters[1], 1u);
         __syncthreads(); // every thread has read fail and wsum: the chunk tables may overwrite the union's LDS
         return false;
     }
@@ -581,9 +592,29 @@ __device__ bool stageBlockUnion(const BlockLane& bl, const R* __restrict__ rec, 
         sh.dense[excl >> 16]      = uint16_t(t);
     }
     __syncthreads();
-    // 3. this lane's slot entry; the records of the dense entries, a wave per entry
-    uint4 slotEnt = make_uint4(bl.gfirst, 0u, 0u, 0u); // slot 0 and slots past the table
+    // 3. this lane's slot entry {c0, base, mask}; the record of this lane's target: in the slots of this wave whose
+    //    64 sources overlap the group's 64 particles (wave-uniform loop, one or two slots)
+    constexpr unsigned RS    = unsigned(RC) * 16u;    // bytes per record
+    constexpr unsigned spare = unsigned(UCAP) * RS;   // the record past the capacity
+    uint4 slotEnt = make_uint4(0u, 0u, 0u, 0u);
     if (mine) slotEnt = sh.tab[e];
+    unsigned selfAddr = spare, found = 0;
+    for (uint64_t ov = ballot(mine && slotEnt.x + 64u > bl.gfirst && slotEnt.x < bl.gfirst + 64u); ov; ov &= ov - 1)
+    {
+        const int s       = __builtin_ctzll(ov);
+        const unsigned c0 = unsigned(__builtin_amdgcn_readlane(int(slotEnt.x), s));
+        const unsigned b  = unsigned(__builtin_amdgcn_readlane(int(slotEnt.y), s));
+        const uint64_t m  = uint64_t(unsigned(__builtin_amdgcn_readlane(int(slotEnt.w), s))) << 32 |
+                           unsigned(__builtin_amdgcn_readlane(int(slotEnt.z), s));
+        const unsigned d  = bl.gfirst + lane - c0;
+        if (d < 64u && ((m >> d) & 1))
+        {
+            selfAddr = (b + unsigned(__popcll(m & ((1ull << d) - 1ull)))) * RS;
+            ++found;
+        }
+    }
+    bl.selfAddr = selfAddr;
+    if (found > 1u) sh.fail = 1u; // (the self test is by record: a target staged twice cannot be told from a neighbor)
     for (unsigned k = wave; k < nent; k += NG)
     {
         const uint4 en   = sh.tab[sh.dense[k]];
@@ -598,8 +629,14 @@ __device__ bool stageBlockUnion(const BlockLane& bl, const R* __restrict__ rec, 
         }
     }
     __syncthreads();
-    // 4. the hash becomes the slot tables
-    sh.tab[t] = slotEnt;
+    const bool staged = sh.fail == 0u;
+    if (counters && t == 0) atomicAdd(&counters[staged ? 0 : 1], 1u);
+    __syncthreads(); // (every thread has read fail, and is done with the hash)
+    if (!staged) return false;
+    // 4. the hash becomes the slot tables: per half of the slot's sources, the byte offset of its first record and its
+    //    mask; slot 0 and the slots past the table decode to the spare record
+    sh.tab[t] = mine ? make_uint4(slotEnt.y * RS, slotEnt.z, (slotEnt.y + unsigned(__popc(slotEnt.z))) * RS, slotEnt.w)
+                     : make_uint4(spare, 0u, spare, 0u);
     __syncthreads();
     return true;
 }
@@ -615,37 +652,38 @@ __device__ void forEachNeighborUnion(const PackedLane& pl, const BlockLane& bl,
     if (nblk == 0) return;
     const uint4* wtab = sh.tab + (threadIdx.x >> 6) * 64;
     int4 w            = pl.block(0);
+    constexpr unsigned RS = unsigned(RC) * 16u, spare = unsigned(UCAP) * RS;
+    const char* recs      = reinterpret_cast<const char*>(sh.rec);
+    const unsigned self   = bl.selfAddr;
     auto batch = [&](int w0, int w1)
     {
         const uint32_t ws[2] = {uint32_t(w0), uint32_t(w1)};
-        unsigned j[4];
+        unsigned a[4];
         R rr[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
         {
-            const uint32_t code = (ws[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;
-            // (a staged group has at most kBuSlots slots: the masked slot stays inside the wave's table)
-            const unsigned slot = code & (kBuSlots - 1u), off = code >> kChunkSlotBits;
+            // code = slot | off << 10 in the low or the high half of the word. A staged group has at most kBuSlots
+            // slots: the masked slot stays inside the wave's table. The shift counts take the low five bits of off.
+            const uint32_t wd   = ws[u >> 1];
+            const bool hiHalf   = u & 1;
+            const unsigned slot = (hiHalf ? wd >> 16 : wd) & (kBuSlots - 1u);
+            const unsigned sh5  = (hiHalf ? wd >> 26 : wd >> kChunkSlotBits) & 31u;
+            const bool upper    = hiHalf ? int32_t(wd) < 0 : (wd & 0x8000u) != 0u;
             const uint4 en      = wtab[slot];
-            const uint32_t below = (1u << (off & 31u)) - 1u;
-            const bool upper     = off >= 32u;
-            const uint32_t lo = upper ? en.z : en.z & below, hi = upper ? en.w & below : 0u;
-            unsigned p        = en.y + unsigned(__popc(lo)) + unsigned(__popc(hi));
-            j[u]              = en.x + off;
+            const uint32_t m    = (upper ? en.w : en.y) & ~(~0u << sh5);
+            a[u]                = (upper ? en.z : en.x) + unsigned(__popc(m)) * RS;
 #ifdef SPHX_DEVICE_CHECKS
-            const bool ok = (code & kChunkSlotMask) < max(bl.nch, 1u) && p < unsigned(UCAP) &&
-                            ((code & kChunkSlotMask) != 0u || j[u] == pl.self);
+            const unsigned code = (hiHalf ? wd >> 16 : wd) & 0xFFFFu;
+            const bool ok       = (code & kChunkSlotMask) < max(bl.nch, 1u) && a[u] <= spare &&
+                            ((code & kChunkSlotMask) != 0u || a[u] == spare);
             SPHX_DCHECK(ok, 0);
-            if (!ok)
-            {
-                p    = 0u;
-                j[u] = pl.self;
-            }
+            if (!ok) a[u] = spare;
 #endif
             uint4 o4[RC];
 #pragma unroll
             for (int c = 0; c < RC; ++c)
-                o4[c] = sh.rec[p * RC + c];
+                o4[c] = *reinterpret_cast<const uint4*>(recs + a[u] + c * 16);
             float4 o[RC];
 #pragma unroll
             for (int c = 0; c < RC; ++c)
@@ -657,7 +695,8 @@ __device__ void forEachNeighborUnion(const PackedLane& pl, const BlockLane& bl,
         for (int u = 0; u < 4; ++u)
         {
             pinRegs(rr[u]);
-            if (j[u] != pl.self) f(j[u], rr[u]);
+            // (the loops staged this way do not use the source index: the body gets the target's)
+            if (a[u] != self && a[u] != spare) f(pl.self, rr[u]);
         }
     };
     for (unsigned b = 0; b < nblk; ++b)
@@ -667,7 +706,6 @@ __device__ void forEachNeighborUnion(const PackedLane& pl, const BlockLane& bl,
         batch(w.z, w.w);
         w = wn;
     }
-    (void)bl;
 }
 
 /*! @brief loader of a block-union kernel: staged blocks read the LDS union, the others gather per lane (the loop of

@@ -1227,9 +1227,28 @@ SPHX_HD void veDefGradhJLoop(unsigned i, double K, const G& box, const Idx* nbr,
     reduceAcross(ld, kxi, whomegai, wrho0i);
     // the kernel scale, then the target's own terms: W(0) = 1, dW(0) = 0
     const HT invS = HT(1) / kf.wqScale();
-    kxi      = xmi + kxi * invS;
-    whomegai = -HT(3) * xmi + whomegai * invS;
-    wrho0i   = -HT(3) * mi + wrho0i * invS;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (std::is_same_v<KF, KernelFnSinc6> && std::is_same_v<HT, float>)
+    {
+        // The rounding of the production instance, written out: the scaled sums are rounded before the own terms
+        // are added (kx) or fused with them (the other two). Left to the compiler, which of these products it
+        // contracts depends on the basic block the neighbor loop exits into, and the kernels built on this loop
+        // (gathered, block-union staged with its two loops) must give the same bits.
+        HT sk = kxi * invS, sw = whomegai * invS, sr = wrho0i * invS;
+        pinRegs(sk);
+        pinRegs(sw);
+        pinRegs(sr);
+        kxi      = xmi + sk;
+        whomegai = fmaf(-HT(3), xmi, sw);
+        wrho0i   = fmaf(-HT(3), mi, sr);
+    }
+    else
+#endif
+    {
+        kxi      = xmi + kxi * invS;
+        whomegai = -HT(3) * xmi + whomegai * invS;
+        wrho0i   = -HT(3) * mi + wrho0i * invS;
+    }
     HT Kf = HT(K);
     kxi *= Kf * h3Inv;
     whomegai *= Kf * h3Inv * hInv;
