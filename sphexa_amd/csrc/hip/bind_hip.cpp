@@ -385,8 +385,9 @@ PYBIND11_MODULE(_sphx_hip, m)
           py::arg("vz") = 0, py::arg("eosTemp") = 0, py::arg("eosPrho") = 0, py::arg("eosC") = 0,
           py::arg("eosRho") = 0, py::arg("eosP") = 0);
     m.def("set_staged", [](unsigned mask) { setStaged(mask); },
-          "pair loops that run LDS-staged: bit 0 XMass, 1 Gradh, 2 IAD, 3 AV, 4 momentum, 5 IAD and AV also on 256-thread "
-          "blocks (hydro.hip, staged.h)");
+          "pair loops that run LDS-staged (block-union staging: hydro.hip, staged.h): bit 1 Gradh, 2 IAD, 3 AV, 6 XMass; "
+          "bit 5: these loops also in runs on 256-thread blocks; bit 4 (momentum) has no staged loop; bit 0 is unused "
+          "(it selected the per-group staged XMass, removed). Default 78");
     m.def("staged_mask", []() { return stagedMask(); });
     m.def("set_staged_counters", [](Ptr counters) { setStagedCounters(P<unsigned>(counters)); },
           "two uint32 device counters of the block-union loops (blocks staged, blocks fallen back to the gathered "

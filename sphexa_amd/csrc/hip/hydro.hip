@@ -32,59 +32,18 @@ namespace sphx::hip
 #endif
 constexpr int kBlock = SPHX_PAIR_BLOCK; // threads per block of the pair loops (4 target groups)
 
-/*! @brief target of this thread and its neighbor list (chunk-coded rows of its 64-particle group, packed_list.hpp).
- *         The wave loads its group's chunk table into LDS (nch entries, one coalesced load per 64). Threads past the
- *         last target stay alive with an empty list and a clamped index (the cooperative gathers need all 64 lanes of
- *         a wave); they store nothing. `n` is the neighbor count (excluding self, capped).
+/*! @brief target of this thread and its neighbor list (chunk-coded rows of its 64-particle group, packed_list.hpp):
+ *         groupTargetOf (staged.h), then the wave loads its group's chunk table into LDS. Threads past the last target
+ *         stay alive with an empty list and a clamped index (the cooperative gathers need all 64 lanes of a wave).
  */
 template<int B = kBlock>
 __device__ __forceinline__ bool targetOf(const NbrArgs& a, int64_t& i, PackedLane& pl, unsigned& n)
 {
     __shared__ uint32_t ctabAll[B / 64][kChunkCap];
-    unsigned lb     = xcdRemap(blockIdx.x, gridDim.x);
-    int64_t t       = int64_t(lb) * B + threadIdx.x;
-    i               = a.first + t;
-    const int64_t g = t >> 6;
-    const int64_t G = (a.last - a.first + 63) / 64;
-    const unsigned lane = threadIdx.x & 63;
-    const int32_t* tab  = a.nidx + g * int64_t(packedTableInts(a.ngmax));
-    const int32_t* rowsInt = a.nidx + packedTableRegion(G, a.ngmax);
-    // wave-uniform: waves past the last group have no table
-    unsigned nch = 0, T = 0;
-    pl.nblk = 0;
-    if (g < G)
-    {
-        pl.nblk          = unsigned(*(const __attribute__((address_space(4))) int32_t*)(tab));
-        const unsigned w = unsigned(*(const __attribute__((address_space(4))) int32_t*)(tab + 1));
-        nch              = min(tableWordNch(w), kChunkCap);
-        T                = tableWordT(w);
-    }
-    pl.tab  = tab + 2 + T;
-    pl.rows = reinterpret_cast<const int4*>(rowsInt) + lane;
-    uint32_t* ctab = ctabAll[threadIdx.x >> 6];
-    for (unsigned e = lane; e < nch; e += 64)
-    {
-        const int32_t r = *(const __attribute__((address_space(4))) int32_t*)(tab + 2 + (e >> 8));
-        ctab[e]         = uint32_t(rowsInt[size_t(r) * 256 + (e & 255)]);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    pl.ctab = ctab;
-#ifdef SPHX_DEVICE_CHECKS
-    pl.ntot = a.ntot;
-    SPHX_DCHECK(pl.nblk <= listBlocksMax(a.ngmax), 1);
-    pl.nblk = min(pl.nblk, listBlocksMax(a.ngmax));
-#endif
-    if (i >= a.last)
-    {
-        i       = a.last - 1;
-        pl.self = unsigned(i);
-        n       = 0;
-        return false;
-    }
-    pl.self = unsigned(i);
-    int cnt = a.nc[i] - 1;
-    n       = unsigned(cnt < 0 ? 0 : (unsigned(cnt) < a.ngmax ? cnt : a.ngmax));
-    return true;
+    BlockLane bl;
+    const bool valid = groupTargetOf<B>(a, i, pl, n, bl);
+    loadChunkTable(bl, pl, ctabAll[threadIdx.x >> 6]);
+    return valid;
 }
 
 //! @brief per-wave LDS tile of the cooperative gathers (CoopLoader) for records of type R
@@ -136,6 +95,33 @@ __device__ __forceinline__ CoopLoader<R> coopOf(const R* rec, float4* blockTile,
     return CoopLoader<R>{rec, waveTile<R>(blockTile), unsigned(self)};
 }
 
+/*! @brief source policy of a pair-loop body: every lane gathers its neighbors' records from global memory, above
+ *         SPHX_COOP_MIN_CHUNKS 64 lanes cooperating per record (CoopLoader). Its LDS (the waves' chunk tables, the
+ *         gather tiles, the epilogue's row staging) is declared where it is used, one variable each, so that a kernel
+ *         holds only what its instance reads. UnionSource (staged.h) is the other policy. */
+template<class R, int B>
+struct GatheredSource
+{
+    //! targetOf<B> (`valid`); never staged. The group's header is the union policy's
+    __device__ __forceinline__ bool open(const NbrArgs& a, const R*, int64_t& i, PackedLane& pl, unsigned& n,
+                                         BlockLane&, bool& valid) const
+    {
+        valid = targetOf<B>(a, i, pl, n);
+        return false;
+    }
+    __device__ __forceinline__ CoopLoader<R> loader(const R* rec, int64_t self, const BlockLane&, bool) const
+    {
+        __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
+        return CoopLoader<R>{rec, waveTile<R>(tile), unsigned(self)};
+    }
+    //! this wave's 64 x 5 float4 of row staging for an epilogue's record writes (iadEpilogue)
+    __device__ __forceinline__ float4* epilogueRows() const
+    {
+        __shared__ float4 rows[B / 64][64 * 5];
+        return rows[threadIdx.x >> 6];
+    }
+};
+
 //! @brief the launchers' view of the neighbor arguments with the record count set
 inline NbrArgs withTot(NbrArgs a, int64_t ntot)
 {
@@ -172,10 +158,22 @@ static const unsigned kPairMask = []
 
 void setPairBlock(int block) { g_pairBlock = block == 512 ? 512 : kBlock; }
 
-/* Loops that run LDS-staged (staged.h), fixed-point path only: bit 0 XMass (one group per workgroup, W waves; slower
- * than the gathered loop, kept for A/B), bit 1 Gradh, bit 2 IAD, bit 3 the AV switches and bit 6 XMass (block-union
- * staging: the source union of the block's groups in LDS, one wave per group, results bit-identical to the gathered
- * loops; bit 6 wins over bit 0). Bit 4 (momentum) has no staged loop: it gathers. Bit 5: the block-union loops also in
+//! whether loop `loop` (bit of kPairMask) takes its large block in this run
+static bool largeBlockOn(int loop) { return g_pairBlock == 512 && ((kPairMask >> loop) & 1u); }
+
+/*! @brief f(std::integral_constant<int, B>, more...) with the block size B of loop `loop` in this run: L, the loop's
+ *         large block size, where the loop takes it, else kBlock */
+template<int L, class F, class... A>
+inline void withPairBlock(int loop, F&& f, A... more)
+{
+    if (largeBlockOn(loop)) f(std::integral_constant<int, L>{}, more...);
+    else f(std::integral_constant<int, kBlock>{}, more...);
+}
+
+/* Loops that run LDS-staged (staged.h), fixed-point path only: bit 1 Gradh, bit 2 IAD, bit 3 the AV switches and bit 6
+ * XMass (block-union staging: the source union of the block's groups in LDS, one wave per group, results bit-identical
+ * to the gathered loops). Bit 0 is unused (it selected a per-group staged XMass, removed: profiles/r6/staged/README.md).
+ * Bit 4 (momentum) has no staged loop: it gathers. Bit 5: the block-union loops also in
  * runs on 256-thread blocks (setPairBlock: self-gravity); without it such runs gather: the union of 4 groups (~1300
  * records on a lattice, ~1700 on a glass) does not fit the LDS of four blocks per CU with the 32-B records of IAD and AV
  * (profiles/r7/staged_block/README.md); with the 16-B records of XMass and Gradh it fits, at half the gathered loops'
@@ -194,9 +192,8 @@ unsigned stagedMask() { return g_staged; }
 //! whether loop `loop` (0 XMass, 1 Gradh, 2 IAD, 3 AV) runs its block-union kernel in this run
 static bool unionLoopOn(int loop)
 {
-    const bool big     = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
-    const unsigned bit = loop == 0 ? 6u : unsigned(loop); // (bit 0 is the per-group staged XMass)
-    return ((g_staged >> bit) & 1u) && (big || (g_staged & 32u));
+    const unsigned bit = loop == 0 ? 6u : unsigned(loop);
+    return ((g_staged >> bit) & 1u) && (largeBlockOn(loop) || (g_staged & 32u));
 }
 
 // tests: blocks staged / fallen back by the block-union loops (one atomic per block); null in production
@@ -245,16 +242,6 @@ static const int kXgBlock = []
     return (e ? std::atoi(e) : SPHX_STB_XG_BLOCK) == 512 ? 512 : 1024;
 }();
 
-//! @brief f(std::integral_constant<int, B>) with the block size of the block-union XMass / Gradh loop of this run
-template<class F>
-inline void withXgBlock(F&& f, int loop)
-{
-    const bool big = g_pairBlock == 512 && ((kPairMask >> loop) & 1u);
-    if (!big) f(std::integral_constant<int, kBlock>{});
-    else if (kXgBlock == 512) f(std::integral_constant<int, 512>{});
-    else f(std::integral_constant<int, 1024>{});
-}
-
 // tests: the search stores the slot masks even when no staged loop runs (packed-list format checks)
 static bool g_listMasks = false;
 void setListMasks(bool on) { g_listMasks = on; }
@@ -262,26 +249,7 @@ bool listMasksForced() { return g_listMasks; }
 // the search stores the slot masks (16 B per particle) only while a loop of this run reads them
 bool listMasksWanted()
 {
-    return g_listMasks || (g_staged & 1u) || unionLoopOn(0) || unionLoopOn(1) || unionLoopOn(2) || unionLoopOn(3);
-}
-
-//! grid of a staged loop: one workgroup per target group
-inline unsigned gridStaged(const NbrArgs& a) { return unsigned((a.last - a.first + 63) / 64); }
-
-//! @brief f(std::integral_constant<int, B>) with the run's block size B for loop `loop` (bit of kPairMask)
-template<class F>
-inline void withPairBlock(F&& f, int loop = 0)
-{
-    if (g_pairBlock == 512 && ((kPairMask >> loop) & 1u)) f(std::integral_constant<int, 512>{});
-    else f(std::integral_constant<int, kBlock>{});
-}
-
-//! @brief as withPairBlock, with block size L instead of 512 (a loop whose occupancy fits other multiples of 64)
-template<int L, class F>
-inline void withPairBlockL(F&& f, int loop)
-{
-    if (g_pairBlock == 512 && ((kPairMask >> loop) & 1u)) f(std::integral_constant<int, L>{});
-    else f(std::integral_constant<int, kBlock>{});
+    return g_listMasks || unionLoopOn(0) || unionLoopOn(1) || unionLoopOn(2) || unionLoopOn(3);
 }
 
 // ------------------------------------------------------------------------------------------------- packing
@@ -578,17 +546,19 @@ __global__ __launch_bounds__(kBlock) void xmassKernel(NbrArgs a, SphConsts sc, B
 }
 
 //! @brief XMass on fixed-point records (see SrcPosQ): same sum as xmassJLoop (sph_math.hpp), half the gathers
-template<int B = kBlock, int kKf = 0>
-__global__ __launch_bounds__(B) void xmassQKernel(NbrArgs a, SphConsts sc, QFrame q, const float* __restrict__ h,
-                                                  const SrcPosQ* __restrict__ rec, const float* __restrict__ wh,
-                                                  float* __restrict__ xm, SrcXmQ* __restrict__ xmOut)
+template<int kKf, class Src>
+__device__ __forceinline__ void xmassQBody(Src src, const NbrArgs& a, const SphConsts& sc, const QFrame& q,
+                                           const float* h, const SrcPosQ* rec,
+                                           const float* wh, float* xm,
+                                           SrcXmQ* xmOut)
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<SrcPosQ>::S];
     int64_t i;
     PackedLane pl;
     unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
-    const auto ld    = coopOf(rec, tile, i, a);
+    BlockLane bl;
+    bool valid;
+    const bool staged = src.open(a, rec, i, pl, n, bl, valid);
+    const auto ld    = src.loader(rec, i, bl, staged);
     const SrcPosQ pi = ld(unsigned(i));
     const float hi = h[i], hInv = 1.f / hi, h3Inv = hInv * hInv * hInv;
     // quarter arguments u = r / (4h): the quantum and 1/(4h) folded into one scale per dimension (KernelFn::wq)
@@ -610,86 +580,26 @@ __global__ __launch_bounds__(B) void xmassQKernel(NbrArgs a, SphConsts sc, QFram
     if (xmOut) xmOut[i] = SrcXmQ{pi.x, pi.y, pi.z, v}; // Gradh's record of this target
 }
 
-/*! @brief XMass, LDS-staged (staged.h): W waves per group, the group's SrcPosQ union in LDS. Same sum as xmassQKernel
- *         (summed in W partial sums, the target's own term last). */
-template<int W, int UCAP>
-__global__ __launch_bounds__(64 * W) void xmassQStagedKernel(NbrArgs a, SphConsts sc, QFrame q,
-                                                             const float* __restrict__ h,
-                                                             const SrcPosQ* __restrict__ rec,
-                                                             const float* __restrict__ wh, float* __restrict__ xm,
-                                                             SrcXmQ* __restrict__ xmOut)
+template<int B = kBlock, int kKf = 0>
+__global__ __launch_bounds__(B) void xmassQKernel(NbrArgs a, SphConsts sc, QFrame q, const float* __restrict__ h,
+                                                  const SrcPosQ* __restrict__ rec, const float* __restrict__ wh,
+                                                  float* __restrict__ xm, SrcXmQ* __restrict__ xmOut)
 {
-    using Ld = StagedLoader<SrcPosQ, W, UCAP>;
-    __shared__ typename Ld::Shared sh;
-    int64_t i;
-    StagedLane sl;
-    unsigned n;
-    const bool valid = stagedTargetOf<W>(a, i, sl, n);
-    const Ld ld{rec, nullptr, 0.f, &sh};
-    const KernelFn kf{wh, nullptr, sc.sincIndex, sc.kernelChoice};
-    const SrcPosQ pi = ld(unsigned(i));
-    const float hi = h[i], hInv = 1.f / hi, h3Inv = hInv * hInv * hInv;
-    const float sx = q.inv[0] * 0.25f * hInv, sy = q.inv[1] * 0.25f * hInv, sz = q.inv[2] * 0.25f * hInv;
-    float rho0 = 0.f;
-    forEachNeighbor<SPHX_BATCH_POS>(&sl, 0, n, ld, [&](unsigned, const SrcPosQ& pj) {
-        const float ux = float(int32_t(pi.x - pj.x)) * sx;
-        const float uy = float(int32_t(pi.y - pj.y)) * sy;
-        const float uz = float(int32_t(pi.z - pj.z)) * sz;
-        rho0 += kf.wqIn(sqrtF(ux * ux + uy * uy + uz * uz)) * pj.m;
-    });
-    reduceAcross(ld, rho0);
-    rho0 = pi.m + rho0 / kf.wqScale();
-    if (!valid || threadIdx.x >= 64) return;
-    const float v = pi.m / (rho0 * float(sc.K) * h3Inv);
-    xm[i]         = v;
-    if (xmOut) xmOut[i] = SrcXmQ{pi.x, pi.y, pi.z, v};
+    xmassQBody<kKf>(GatheredSource<SrcPosQ, B>{}, a, sc, q, h, rec, wh, xm, xmOut);
 }
 
-/*! @brief xmassQKernel with the block's SrcPosQ union staged in LDS (staged.h, block-union staging: one wave per
- *         group, a block whose union does not fit runs the gathered loop). Same sum in the same order. */
+/*! @brief xmassQKernel with the block's SrcPosQ union staged in LDS (staged.h: one wave per group, a block whose union
+ *         does not fit runs the gathered loop). Same sum in the same order. */
 // (the 1024-thread shape needs 8 waves per SIMD, i.e. at most 64 VGPRs, for its two blocks per CU)
 template<int B, int kKf, int UCAP>
 __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(B == 1024 ? 8 : 4))) void xmassQUnionKernel(
     NbrArgs a, SphConsts sc, QFrame q, const float* __restrict__ h, const SrcPosQ* __restrict__ rec,
     const float* __restrict__ wh, float* __restrict__ xm, SrcXmQ* __restrict__ xmOut, unsigned* counters)
 {
-    using Ld = BlockUnionLoader<SrcPosQ, B / 64, UCAP>;
-    __shared__ typename Ld::Shared sh;
-    int64_t i;
-    PackedLane pl;
-    BlockLane bl;
-    unsigned n;
-    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
-    const bool staged = stageBlockUnion<SrcPosQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
-    if (!staged) loadChunkTable(bl, pl, sh);
-    const Ld ld{rec, &sh, &bl, staged};
-    const SrcPosQ pi = ld(unsigned(i));
-    const float hi = h[i], hInv = 1.f / hi, h3Inv = hInv * hInv * hInv;
-    const float sx = q.inv[0] * 0.25f * hInv, sy = q.inv[1] * 0.25f * hInv, sz = q.inv[2] * 0.25f * hInv;
-    float rho0 = 0.f;
-    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        float sum = 0.f;
-        forEachNeighbor<SPHX_BATCH_POS>(&pl, 0, n, ld, [&](unsigned, const SrcPosQ& pj) {
-            const float ux = float(int32_t(pi.x - pj.x)) * sx;
-            const float uy = float(int32_t(pi.y - pj.y)) * sy;
-            const float uz = float(int32_t(pi.z - pj.z)) * sz;
-            sum += kf.wqIn(sqrtF(ux * ux + uy * uy + uz * uz)) * pj.m;
-        });
-        rho0 = pi.m + sum / kf.wqScale();
-    });
-    if (!valid) return;
-    const float v = pi.m / (rho0 * float(sc.K) * h3Inv);
-    xm[i]         = v;
-    if (xmOut) xmOut[i] = SrcXmQ{pi.x, pi.y, pi.z, v}; // Gradh's record of this target
+    using Src = UnionSource<SrcPosQ, B, UCAP>;
+    __shared__ typename Src::Shared sh;
+    xmassQBody<kKf>(Src{sh, counters}, a, sc, q, h, rec, wh, xm, xmOut);
 }
-
-// staged shapes (waves per group, union capacity in records), per loop
-#ifndef SPHX_ST_XMASS_W
-#define SPHX_ST_XMASS_W 4
-#endif
-#ifndef SPHX_ST_XMASS_U
-#define SPHX_ST_XMASS_U 1024
-#endif
 
 //! VE equation of state fused into the Gradh loop's epilogue (eosVeKernel per target; temp == nullptr: not fused)
 struct EosOut
@@ -731,6 +641,30 @@ __device__ __forceinline__ void gradhEpilogue(int64_t i, const SphConsts& sc, co
     }
 }
 
+//! @brief the Gradh loop (veDefGradhJLoop, sph_math.hpp) and its fused epilogue for the target of this thread
+template<int kKf, class Src, class R, class G>
+__device__ __forceinline__ void veDefGradhBody(Src src, const NbrArgs& a, const SphConsts& sc, const G& box,
+                                               const float* h, const R* rec,
+                                               const float* wh, const float* whd,
+                                               float* kx, float* gradh, float mUniform,
+                                               const float* vx, const float* vy,
+                                               const float* vz, SrcIadQ* iadOut,
+                                               const EosOut& eos)
+{
+    int64_t i;
+    PackedLane pl;
+    unsigned n;
+    BlockLane bl;
+    bool valid;
+    const bool staged = src.open(a, rec, i, pl, n, bl, valid);
+    const auto ld    = src.loader(rec, i, bl, staged);
+    float k, g;
+    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
+                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], ld, kf, k, g, mUniform); });
+    if (!valid) return;
+    gradhEpilogue(i, sc, rec, k, g, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
+}
+
 template<class R, class G, int B = kBlock, int kKf = 0>
 __global__ __launch_bounds__(B) void veDefGradhKernel(NbrArgs a, SphConsts sc, G box,
                                                            const float* __restrict__ h, const R* __restrict__ rec,
@@ -740,21 +674,12 @@ __global__ __launch_bounds__(B) void veDefGradhKernel(NbrArgs a, SphConsts sc, G
                                                            const float* __restrict__ vy, const float* __restrict__ vz,
                                                            SrcIadQ* __restrict__ iadOut, EosOut eos = EosOut{})
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
-    int64_t i;
-    PackedLane pl;
-    unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
-    float k, g;
-    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
-                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], coopOf(rec, tile, i, a), kf, k, g, mUniform); });
-    if (!valid) return;
-    gradhEpilogue(i, sc, rec, k, g, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
+    veDefGradhBody<kKf>(GatheredSource<R, B>{}, a, sc, box, h, rec, wh, whd, kx, gradh, mUniform, vx, vy, vz, iadOut,
+                        eos);
 }
 
-/*! @brief veDefGradhKernel on SrcXmQ records with the block's source union staged in LDS (staged.h, block-union
- *         staging; a block whose union does not fit runs the gathered loop). Same sums in the same order, the same
- *         fused epilogue. */
+/*! @brief veDefGradhKernel on SrcXmQ records with the block's source union staged in LDS (staged.h; a block whose
+ *         union does not fit runs the gathered loop). Same sums in the same order, the same fused epilogue. */
 template<int B, int kKf, int UCAP>
 __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(B == 1024 ? 8 : 4))) void veDefGradhUnionKernel(
     NbrArgs a, SphConsts sc, QFrame box, const float* __restrict__ h, const SrcXmQ* __restrict__ rec,
@@ -762,20 +687,9 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(B == 1024 ? 8
     float mUniform, const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
     SrcIadQ* __restrict__ iadOut, EosOut eos, unsigned* counters)
 {
-    using Ld = BlockUnionLoader<SrcXmQ, B / 64, UCAP>;
-    __shared__ typename Ld::Shared sh;
-    int64_t i;
-    PackedLane pl;
-    BlockLane bl;
-    unsigned n;
-    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
-    const bool staged = stageBlockUnion<SrcXmQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
-    if (!staged) loadChunkTable(bl, pl, sh);
-    float k, g;
-    withKernelFn<kKf>(sc, wh, whd, [&](const auto& kf)
-                 { veDefGradhJLoop(unsigned(i), sc.K, box, &pl, 0, n, h[i], Ld{rec, &sh, &bl, staged}, kf, k, g, mUniform); });
-    if (!valid) return;
-    gradhEpilogue(i, sc, rec, k, g, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
+    using Src = UnionSource<SrcXmQ, B, UCAP>;
+    __shared__ typename Src::Shared sh;
+    veDefGradhBody<kKf>(Src{sh, counters}, a, sc, box, h, rec, wh, whd, kx, gradh, mUniform, vx, vy, vz, iadOut, eos);
 }
 
 __global__ void eosVeKernel(int64_t first, int64_t last, SphConsts sc, const double* __restrict__ temp,
@@ -968,7 +882,10 @@ __device__ __forceinline__ void iadEpilogue(const NbrArgs& a, bool valid, int64_
     }
 }
 
-//! @brief IAD matrix, then divv/curlv (+ velocity gradient) in the same kernel over the same neighbor list
+/*! @brief IAD matrix, then divv/curlv (+ velocity gradient) in the same kernel over the same neighbor list.
+ *         This loop keeps its text in both kernels, each on its source policy: as one body function that the kernels
+ *         pass their arguments to, the two pointer sets (cij, dV) are read before the neighbor loop and held in 10-24
+ *         SGPRs across it, and the instances' registers and occupancy move (profiles/r9/pair_sources/README.md). */
 template<bool kAvS, class R, class G, int B = kBlock, int kKf = 0>
 __global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc, G box,
                                                              const float* __restrict__ h,
@@ -982,29 +899,27 @@ __global__ __launch_bounds__(B) void iadDivvCurlvKernel(NbrArgs a, SphConsts sc,
                                                              const float* __restrict__ prho,
                                                              SrcMomSide* __restrict__ momSide = nullptr)
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<R>::S];
+    const GatheredSource<R, B> src{};
     int64_t i;
     PackedLane pl;
     unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
+    BlockLane bl;
+    bool valid;
+    const bool staged = src.open(a, rec, i, pl, n, bl, valid);
     float c[6], g[6], dvi, cvi, S[3];
     withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], coopOf(rec, tile, i, a), kf, c, dvi,
-                                cvi, g, S);
+        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], src.loader(rec, i, bl, staged), kf, c,
+                                dvi, cvi, g, S);
     });
     float4* w = nullptr;
-    if constexpr (std::is_same_v<R, SrcIadQ>)
-    {
-        __shared__ float4 stage[B / 64][64 * 5];
-        w = stage[threadIdx.x >> 6];
-    }
+    if constexpr (std::is_same_v<R, SrcIadQ>) w = src.epilogueRows();
     iadEpilogue<kAvS>(a, valid, i, h, kx, rec, cij, divv, curlv, dV, doGrad, avS, avOut, momOut, cs, mm, prho, momSide,
                       c, g, dvi, cvi, S, w);
 }
 
-/*! @brief iadDivvCurlvKernel on SrcIadQ records with the block's source union staged in LDS (staged.h, block-union
- *         staging; a block whose union does not fit runs the gathered loop). Same sums in the same order. The
- *         epilogue's row staging reuses the records' LDS. */
+/*! @brief iadDivvCurlvKernel on SrcIadQ records with the block's source union staged in LDS (staged.h; a block whose
+ *         union does not fit runs the gathered loop). Same sums in the same order. The epilogue's row staging reuses
+ *         the records' LDS. */
 template<bool kAvS, int B, int kKf, int UCAP>
 __global__ __launch_bounds__(B) void iadDivvCurlvUnionKernel(NbrArgs a, SphConsts sc, QFrame box,
                                                              const float* __restrict__ h,
@@ -1018,23 +933,22 @@ __global__ __launch_bounds__(B) void iadDivvCurlvUnionKernel(NbrArgs a, SphConst
                                                              const float* __restrict__ prho,
                                                              SrcMomSide* __restrict__ momSide, unsigned* counters)
 {
-    using Ld = BlockUnionLoader<SrcIadQ, B / 64, UCAP>;
-    __shared__ typename Ld::Shared sh;
-    static_assert(sizeof(sh.rec) >= sizeof(float4) * (B / 64) * 64 * 5, "the epilogue's rows fit the records' LDS");
+    using Src = UnionSource<SrcIadQ, B, UCAP>;
+    __shared__ typename Src::Shared sh;
+    Src src{sh, counters};
     int64_t i;
     PackedLane pl;
-    BlockLane bl;
     unsigned n;
-    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
-    const bool staged = stageBlockUnion<SrcIadQ, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
-    if (!staged) loadChunkTable(bl, pl, sh);
+    BlockLane bl;
+    bool valid;
+    const bool staged = src.open(a, rec, i, pl, n, bl, valid);
     float c[6], g[6], dvi, cvi, S[3];
     withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], Ld{rec, &sh, &bl, staged}, kf, c, dvi,
-                                cvi, g, S);
+        iadDivvCurlvJLoop<kAvS>(unsigned(i), sc.K, box, &pl, 0, n, h[i], kx[i], src.loader(rec, i, bl, staged), kf, c,
+                                dvi, cvi, g, S);
     });
-    __syncthreads(); // every wave is done with the records (or chunk tables)
-    float4* w = reinterpret_cast<float4*>(sh.rec) + (threadIdx.x >> 6) * 64 * 5;
+    __syncthreads(); // every wave is done with the records (or chunk tables): their LDS becomes the epilogue's rows
+    float4* w = src.epilogueRows();
     iadEpilogue<kAvS>(a, valid, i, h, kx, rec, cij, divv, curlv, dV, doGrad, avS, avOut, momOut, cs, mm, prho, momSide,
                       c, g, dvi, cvi, S, w);
 }
@@ -1081,6 +995,37 @@ __global__ __launch_bounds__(kBlock) void avSwitchesQKernel(NbrArgs a, SphConsts
 }
 
 //! @brief AV switches on SrcAvV records (vd = vol divv) with the IAD loop's S_i (avSwitchesVJLoop, sph_math.hpp)
+template<int kKf, class Src>
+__device__ __forceinline__ void avSwitchesVBody(Src src, const NbrArgs& a, const SphConsts& sc, const QFrame& q,
+                                                const float* h, const Six& cij, const SrcAvV* rec,
+                                                const float* divv, const float4* avS,
+                                                const float* wh, double dt,
+                                                const float* alpha, float* alphaOut,
+                                                const double* dtDev, SrcMomQ* momOut,
+                                                SrcMomSide* momSide)
+{
+    int64_t i;
+    PackedLane pl;
+    unsigned n;
+    BlockLane bl;
+    bool valid;
+    const bool staged = src.open(a, rec, i, pl, n, bl, valid);
+    const auto ld    = src.loader(rec, i, bl, staged);
+    if (dtDev) dt = *dtDev;
+    float ci[6]    = {cij.p[0][i], cij.p[1][i], cij.p[2][i], cij.p[3][i], cij.p[4][i], cij.p[5][i]};
+    const float4 s = avS[i - a.first];
+    const float S[3] = {s.x, s.y, s.z};
+    float al;
+    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
+        al = avSwitchesVJLoop(unsigned(i), sc.K, q, &pl, 0, n, h[i], ci, divv[i], S, ld, kf, dt,
+                              sc.alphamin, sc.alphamax, sc.decayConstant, alpha[i]);
+    });
+    if (!valid) return;
+    alphaOut[i] = al;
+    if (momSide) momSide[i].alpha = al;
+    else if (momOut) momOut[i].alpha = al;
+}
+
 template<int B = kBlock, int kKf = 0>
 __global__ __launch_bounds__(B) void avSwitchesVKernel(NbrArgs a, SphConsts sc, QFrame q,
                                                             const float* __restrict__ h, Six cij,
@@ -1093,28 +1038,12 @@ __global__ __launch_bounds__(B) void avSwitchesVKernel(NbrArgs a, SphConsts sc, 
                                                             SrcMomQ* __restrict__ momOut,
                                                             SrcMomSide* __restrict__ momSide = nullptr)
 {
-    __shared__ float4 tile[B / 64 * 64 * CoopLoader<SrcAvV>::S];
-    int64_t i;
-    PackedLane pl;
-    unsigned n;
-    const bool valid = targetOf<B>(a, i, pl, n);
-    if (dtDev) dt = *dtDev;
-    float ci[6]    = {cij.p[0][i], cij.p[1][i], cij.p[2][i], cij.p[3][i], cij.p[4][i], cij.p[5][i]};
-    const float4 s = avS[i - a.first];
-    const float S[3] = {s.x, s.y, s.z};
-    float al;
-    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        al = avSwitchesVJLoop(unsigned(i), sc.K, q, &pl, 0, n, h[i], ci, divv[i], S, coopOf(rec, tile, i, a), kf, dt,
-                              sc.alphamin, sc.alphamax, sc.decayConstant, alpha[i]);
-    });
-    if (!valid) return;
-    alphaOut[i] = al;
-    if (momSide) momSide[i].alpha = al;
-    else if (momOut) momOut[i].alpha = al;
+    avSwitchesVBody<kKf>(GatheredSource<SrcAvV, B>{}, a, sc, q, h, cij, rec, divv, avS, wh, dt, alpha, alphaOut, dtDev,
+                         momOut, momSide);
 }
 
-/*! @brief avSwitchesVKernel with the block's source union staged in LDS (staged.h, block-union staging; a block whose
- *         union does not fit runs the gathered loop). Same sums in the same order. */
+/*! @brief avSwitchesVKernel with the block's source union staged in LDS (staged.h; a block whose union does not fit
+ *         runs the gathered loop). Same sums in the same order. */
 template<int B, int kKf, int UCAP>
 __global__ __launch_bounds__(B) void avSwitchesVUnionKernel(NbrArgs a, SphConsts sc, QFrame q,
                                                             const float* __restrict__ h, Six cij,
@@ -1127,28 +1056,10 @@ __global__ __launch_bounds__(B) void avSwitchesVUnionKernel(NbrArgs a, SphConsts
                                                             SrcMomQ* __restrict__ momOut,
                                                             SrcMomSide* __restrict__ momSide, unsigned* counters)
 {
-    using Ld = BlockUnionLoader<SrcAvV, B / 64, UCAP>;
-    __shared__ typename Ld::Shared sh;
-    int64_t i;
-    PackedLane pl;
-    BlockLane bl;
-    unsigned n;
-    const bool valid  = blockTargetOf<B>(a, i, pl, n, bl);
-    const bool staged = stageBlockUnion<SrcAvV, B / 64, UCAP>(bl, rec, a.ntot, sh, counters);
-    if (!staged) loadChunkTable(bl, pl, sh);
-    if (dtDev) dt = *dtDev;
-    float ci[6]    = {cij.p[0][i], cij.p[1][i], cij.p[2][i], cij.p[3][i], cij.p[4][i], cij.p[5][i]};
-    const float4 s = avS[i - a.first];
-    const float S[3] = {s.x, s.y, s.z};
-    float al;
-    withKernelFn<kKf>(sc, wh, nullptr, [&](const auto& kf) {
-        al = avSwitchesVJLoop(unsigned(i), sc.K, q, &pl, 0, n, h[i], ci, divv[i], S, Ld{rec, &sh, &bl, staged}, kf, dt,
-                              sc.alphamin, sc.alphamax, sc.decayConstant, alpha[i]);
-    });
-    if (!valid) return;
-    alphaOut[i] = al;
-    if (momSide) momSide[i].alpha = al;
-    else if (momOut) momOut[i].alpha = al;
+    using Src = UnionSource<SrcAvV, B, UCAP>;
+    __shared__ typename Src::Shared sh;
+    avSwitchesVBody<kKf>(Src{sh, counters}, a, sc, q, h, cij, rec, divv, avS, wh, dt, alpha, alphaOut, dtDev, momOut,
+                         momSide);
 }
 
 //! @brief block min of the Courant time step, then one atomic per block
@@ -1550,37 +1461,24 @@ void xmass(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t ntot, 
         const QFrame q = qframeOf(box, sc.fixedPoint);
         packRanges(inDone, a, ntot, [&](int64_t lo, int64_t hi)
                    { packPosQKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, m, q, (SrcPosQ*)rec); });
-        if (unionLoopOn(0))
+        // one launch: the block-union kernel or the gathered one, at the block size of this run
+        auto launch = [&](auto bc, auto un)
         {
-            withXgBlock([&](auto bc)
-                        {
-                            constexpr int B = decltype(bc)::value;
-                            withKf(sc, [&](auto kk)
-                                   {
-                                       xmassQUnionKernel<B, decltype(kk)::value, kUnionCapXg<B>>
-                                           <<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcPosQ*)rec, wh,
-                                                                      xm, (SrcXmQ*)xmOut, g_stagedCounters);
-                                   });
-                        }, 0);
-            SPHX_LAUNCH_CHECK();
-            return;
-        }
-        if (g_staged & 1u)
-        {
-            xmassQStagedKernel<SPHX_ST_XMASS_W, SPHX_ST_XMASS_U><<<gridStaged(a), 64 * SPHX_ST_XMASS_W, 0, s>>>(
-                withTot(a, ntot), sc, q, h, (const SrcPosQ*)rec, wh, xm, (SrcXmQ*)xmOut);
-            SPHX_LAUNCH_CHECK();
-            return;
-        }
-        withPairBlockL<SPHX_XMASS_BLOCK>([&](auto bc)
-                      {
-                          constexpr int B = decltype(bc)::value;
-                          withKf(sc, [&](auto kk)
-                                 {
-                                     xmassQKernel<B, decltype(kk)::value><<<gridT(a, B), B, 0, s>>>(
-                                         withTot(a, ntot), sc, q, h, (const SrcPosQ*)rec, wh, xm, (SrcXmQ*)xmOut);
-                                 });
-                      }, 0);
+            withKf(sc, [&](auto kk)
+            {
+                constexpr int B = decltype(bc)::value, KK = decltype(kk)::value;
+                auto go = [&](auto kernel, auto... counters)
+                {
+                    kernel<<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcPosQ*)rec, wh, xm,
+                                                     (SrcXmQ*)xmOut, counters...);
+                };
+                if constexpr (decltype(un)::value) go(xmassQUnionKernel<B, KK, kUnionCapXg<B>>, g_stagedCounters);
+                else go(xmassQKernel<B, KK>);
+            });
+        };
+        if (!unionLoopOn(0)) withPairBlock<SPHX_XMASS_BLOCK>(0, launch, std::false_type{});
+        else if (kXgBlock == 512) withPairBlock<512>(0, launch, std::true_type{});
+        else withPairBlock<1024>(0, launch, std::true_type{});
     }
     SPHX_LAUNCH_CHECK();
 }
@@ -1598,35 +1496,27 @@ void veDefGradh(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t n
         const QFrame q = qframeOf(box, sc.fixedPoint);
         packRanges(inDone, a, ntot, [&](int64_t lo, int64_t hi)
                    { packXmQKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, xm, q, (SrcXmQ*)rec); });
-        if (unionLoopOn(1))
+        auto launch = [&](auto bc, auto un)
         {
-            withXgBlock([&](auto bc)
-                        {
-                            withKf(sc, [&](auto kk)
-                                   {
-                                       // (the runtime kernel function needs 66 VGPRs: 7 waves per SIMD, which is one
-                                       // 1024-thread block per CU; it takes the 512-thread shape)
-                                       constexpr int KK = decltype(kk)::value, B0 = decltype(bc)::value;
-                                       constexpr int B  = KK == 0 && B0 == 1024 ? 512 : B0;
-                                       veDefGradhUnionKernel<B, KK, kUnionCapXg<B>>
-                                           <<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcXmQ*)rec, wh,
-                                                                      whd, kx, gradh, mUniform, vx, vy, vz,
-                                                                      (SrcIadQ*)iadOut, eos, g_stagedCounters);
-                                   });
-                        }, 1);
-            SPHX_LAUNCH_CHECK();
-            return;
-        }
-        withPairBlockL<SPHX_GRADH_BLOCK>([&](auto bc)
-                      {
-                          constexpr int B = decltype(bc)::value;
-                          withKf(sc, [&](auto kk)
-                                 {
-                                     veDefGradhKernel<SrcXmQ, QFrame, B, decltype(kk)::value><<<gridT(a, B), B, 0, s>>>(
-                                         withTot(a, ntot), sc, q, h, (const SrcXmQ*)rec, wh, whd, kx, gradh, mUniform,
-                                         vx, vy, vz, (SrcIadQ*)iadOut, eos);
-                                 });
-                      }, 1);
+            withKf(sc, [&](auto kk)
+            {
+                // (block-union loop: the runtime kernel function needs 66 VGPRs, 7 waves per SIMD, which is one
+                // 1024-thread block per CU; it takes the 512-thread shape)
+                constexpr bool U = decltype(un)::value;
+                constexpr int KK = decltype(kk)::value, B0 = decltype(bc)::value;
+                constexpr int B  = U && KK == 0 && B0 == 1024 ? 512 : B0;
+                auto go = [&](auto kernel, auto... counters)
+                {
+                    kernel<<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, (const SrcXmQ*)rec, wh, whd, kx, gradh,
+                                                     mUniform, vx, vy, vz, (SrcIadQ*)iadOut, eos, counters...);
+                };
+                if constexpr (U) go(veDefGradhUnionKernel<B, KK, kUnionCapXg<B>>, g_stagedCounters);
+                else go(veDefGradhKernel<SrcXmQ, QFrame, B, KK>);
+            });
+        };
+        if (!unionLoopOn(1)) withPairBlock<SPHX_GRADH_BLOCK>(1, launch, std::false_type{});
+        else if (kXgBlock == 512) withPairBlock<512>(1, launch, std::true_type{});
+        else withPairBlock<1024>(1, launch, std::true_type{});
     }
     else
     {
@@ -1712,46 +1602,29 @@ void iadDivvCurlv(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t
                    });
         // fixed-point path: also the S_i of the AV loop (avSwitchesVJLoop) when a workspace is given, and the next
         // loops' own records (avOut / momOut)
-        if (unionLoopOn(2))
+        if (!avS) avOut = nullptr;
+        auto launch = [&](auto bc, auto un)
         {
-            withPairBlock([&](auto bc)
-                          {
-                              constexpr int B = decltype(bc)::value;
-                              withKf(sc, [&](auto kk)
-                              {
-                                  constexpr int KK = decltype(kk)::value;
-                                  if (avS)
-                                      iadDivvCurlvUnionKernel<true, B, KK, kUnionCap<B>><<<gridT(a, B), B, 0, s>>>(
-                                          withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
-                                          dV[0] != nullptr, (float4*)avS, (SrcAvV*)avOut, (SrcMomQ*)momOut, cs, m, prho,
-                                          momSide, g_stagedCounters);
-                                  else
-                                      iadDivvCurlvUnionKernel<false, B, KK, kUnionCap<B>><<<gridT(a, B), B, 0, s>>>(
-                                          withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
-                                          dV[0] != nullptr, nullptr, nullptr, (SrcMomQ*)momOut, cs, m, prho, momSide,
-                                          g_stagedCounters);
-                              });
-                          }, 2);
-            SPHX_LAUNCH_CHECK();
-            return;
-        }
-        withPairBlock([&](auto bc)
-                      {
-                          constexpr int B = decltype(bc)::value;
-                          withKf(sc, [&](auto kk)
-                          {
-                              constexpr int KK = decltype(kk)::value;
-                              if (avS)
-                                  iadDivvCurlvKernel<true, SrcIadQ, QFrame, B, KK><<<gridT(a, B), B, 0, s>>>(
-                                      withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
-                                      dV[0] != nullptr, (float4*)avS, (SrcAvV*)avOut, (SrcMomQ*)momOut, cs, m, prho,
-                                      momSide);
-                              else
-                                  iadDivvCurlvKernel<false, SrcIadQ, QFrame, B, KK><<<gridT(a, B), B, 0, s>>>(
-                                      withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv, curlv, g,
-                                      dV[0] != nullptr, nullptr, nullptr, (SrcMomQ*)momOut, cs, m, prho, momSide);
-                          });
-                      }, 2);
+            withKf(sc, [&](auto kk)
+            {
+                constexpr int B = decltype(bc)::value, KK = decltype(kk)::value;
+                auto go = [&](auto kernel, auto... counters)
+                {
+                    kernel<<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, kx, (const SrcIadQ*)rec, wh, c, divv,
+                                                     curlv, g, dV[0] != nullptr, (float4*)avS, (SrcAvV*)avOut,
+                                                     (SrcMomQ*)momOut, cs, m, prho, momSide, counters...);
+                };
+                if constexpr (decltype(un)::value)
+                {
+                    if (avS) go(iadDivvCurlvUnionKernel<true, B, KK, kUnionCap<B>>, g_stagedCounters);
+                    else go(iadDivvCurlvUnionKernel<false, B, KK, kUnionCap<B>>, g_stagedCounters);
+                }
+                else if (avS) go(iadDivvCurlvKernel<true, SrcIadQ, QFrame, B, KK>);
+                else go(iadDivvCurlvKernel<false, SrcIadQ, QFrame, B, KK>);
+            });
+        };
+        if (unionLoopOn(2)) withPairBlock<512>(2, launch, std::true_type{});
+        else withPairBlock<512>(2, launch, std::false_type{});
     }
     SPHX_LAUNCH_CHECK();
 }
@@ -1783,34 +1656,23 @@ void avSwitches(const NbrArgs& a, const SphConsts& sc, const Box& box, int64_t n
                        packAvVKernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, x, y, z, kx, vx, vy, vz, xm, c, divv,
                                                                            q, (SrcAvV*)rec);
                    });
-        if (unionLoopOn(3))
+        auto launch = [&](auto bc, auto un)
         {
-            withPairBlock([&](auto bc)
-                          {
-                              constexpr int B = decltype(bc)::value;
-                              withKf(sc, [&](auto kk)
-                                     {
-                                         avSwitchesVUnionKernel<B, decltype(kk)::value, kUnionCap<B>>
-                                             <<<gridT(a, B), B, 0, s>>>(
-                                                 withTot(a, ntot), sc, q, h, cc, (const SrcAvV*)rec, divv,
-                                                 (const float4*)avS, wh, dt, alpha, alphaOut, dtDev, (SrcMomQ*)momOut,
-                                                 momSideOf(momOut, ntot, momSplit), g_stagedCounters);
-                                     });
-                          }, 3);
-            SPHX_LAUNCH_CHECK();
-            return;
-        }
-        withPairBlockL<SPHX_AV_BLOCK>([&](auto bc)
-                      {
-                          constexpr int B = decltype(bc)::value;
-                          withKf(sc, [&](auto kk)
-                                 {
-                                     avSwitchesVKernel<B, decltype(kk)::value><<<gridT(a, B), B, 0, s>>>(
-                                         withTot(a, ntot), sc, q, h, cc, (const SrcAvV*)rec, divv, (const float4*)avS,
-                                         wh, dt, alpha, alphaOut, dtDev, (SrcMomQ*)momOut,
-                                         momSideOf(momOut, ntot, momSplit));
-                                 });
-                      }, 3);
+            withKf(sc, [&](auto kk)
+            {
+                constexpr int B = decltype(bc)::value, KK = decltype(kk)::value;
+                auto go = [&](auto kernel, auto... counters)
+                {
+                    kernel<<<gridT(a, B), B, 0, s>>>(withTot(a, ntot), sc, q, h, cc, (const SrcAvV*)rec, divv,
+                                                     (const float4*)avS, wh, dt, alpha, alphaOut, dtDev,
+                                                     (SrcMomQ*)momOut, momSideOf(momOut, ntot, momSplit), counters...);
+                };
+                if constexpr (decltype(un)::value) go(avSwitchesVUnionKernel<B, KK, kUnionCap<B>>, g_stagedCounters);
+                else go(avSwitchesVKernel<B, KK>);
+            });
+        };
+        if (unionLoopOn(3)) withPairBlock<512>(3, launch, std::true_type{});
+        else withPairBlock<SPHX_AV_BLOCK>(3, launch, std::false_type{});
     }
     else
     {
@@ -1836,7 +1698,7 @@ void momentumEnergyVe(const NbrArgs& a, const SphConsts& sc, const Box& box, int
         auto* side      = reinterpret_cast<SrcMomSide*>(static_cast<char*>(rec) + momSideOffset(ntot));
         packRanges(inDone, a, ntot, [&](int64_t lo, int64_t hi)
                    { packMomQ64Kernel<<<gridFor(hi - lo, 256), 256, 0, s>>>(lo, hi, f, q, main, side); });
-        withPairBlock([&](auto bc)
+        withPairBlock<512>(4, [&](auto bc)
                       {
                           constexpr int B = decltype(bc)::value;
                           // 32-bit buffer offsets while the 64-B records fit 4 GiB (Sedov -n 400: 4.1 GB)
@@ -1851,7 +1713,7 @@ void momentumEnergyVe(const NbrArgs& a, const SphConsts& sc, const Box& box, int
                                   momentumEnergyVeQ64Kernel<B, false, KK><<<gridT(a, B), B, 0, s>>>(
                                       withTot(a, ntot), sc, q, main, side, mUniform, wh, ax, ay, az, du, minDt);
                           });
-                      }, 4);
+                      });
         SPHX_LAUNCH_CHECK();
         return;
     }

@@ -26,7 +26,8 @@
  *                of nch; written only while an LDS-staged pair loop is enabled, else T = Tc), ordinals T .. T+nblk-1 the list blocks (row of 64 lanes x 8 codes). Entries past them name
  *                row 0 (valid memory: the pair loops prefetch a block ahead). Every code (s, k) of a list has bit k of
  *                mask s set (s >= 1), so the union of a group's sources is known from the table alone: the LDS-staged
- *                pair loops (hydro.hip StagedGroup) load it once per group.
+ *                pair loops (csrc/hip/staged.h, the block-union prologue stageBlockUnion) merge the masks of a block's
+ *                groups and copy each source into LDS once per block.
  * Rows: group g owns `home` rows (g*home ..), chosen by the host from the previous search's row counts; rows past
  * those come from one of 64 overflow stripes through an atomic counter per stripe (neighbors.hip). The host reads
  * the counters and repeats the search with more overflow rows if a stripe ran out.

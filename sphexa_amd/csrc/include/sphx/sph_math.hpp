@@ -1164,22 +1164,6 @@ __device__ void forEachNeighbor(const PackedLane* plp, int, unsigned, const MomS
 }
 #endif
 
-/*! @brief cross-wave reductions of the LDS-staged loops (csrc/hip/staged.h: W waves split one group's neighbor
- *         lists and add their partial sums after the loop). Every other loader: nothing to do. The J-loops start
- *         their sums at zero and add the target's own term after the reduction, so it is counted once. */
-template<class Ld, class... T>
-SPHX_HD void reduceAcross(const Ld&, T&...)
-{
-}
-template<class Ld, class... T>
-SPHX_HD void reduceAcrossMax(const Ld&, T&...)
-{
-}
-template<class Ld>
-SPHX_HD void reduceAcrossN(const Ld&, HT*, int)
-{
-}
-
 //! @brief xm_i = m_i / rho0_i, rho0_i = K h^-3 sum_j W_ij m_j including self (reference xmass_kern.hpp)
 template<class Idx, class Ld, class KF>
 SPHX_HD HT xmassJLoop(unsigned i, double K, const Box& box, const Idx* nbr, int stride, unsigned nc, HT hi,
@@ -1224,7 +1208,6 @@ SPHX_HD void veDefGradhJLoop(unsigned i, double K, const G& box, const Idx* nbr,
         whomegai += dterh * xmj;
         wrho0i += dterh * massOf(pj, mUniform);
     });
-    reduceAcross(ld, kxi, whomegai, wrho0i);
     // the kernel scale, then the target's own terms: W(0) = 1, dW(0) = 0
     const HT invS = HT(1) / kf.wqScale();
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1400,9 +1383,6 @@ SPHX_HD void iadDivvCurlvJLoop(unsigned i, double K, const G& box, const Idx* nb
         M[2][1] += az * ry;
         M[2][2] += az * rz;
     });
-    reduceAcrossN(ld, tau, 6);
-    reduceAcrossN(ld, &M[0][0], 9);
-    if constexpr (kAvS) reduceAcrossN(ld, S, 3);
     {
         // the kernel scale (KernelFn::wq)
         const HT invS = HT(1) / kf.wqScale();
@@ -1561,8 +1541,6 @@ SPHX_HD HT avSwitchesVJLoop(unsigned i, double K, const G& box, const Idx* nbr, 
         T[1] += wd * ry;
         T[2] += wd * rz;
     });
-    reduceAcross(ld, T[0], T[1], T[2]);
-    reduceAcrossMax(ld, vsig);
     {
         const HT invS = HT(1) / kf.wqScale(); // (KernelFn::wq)
         T[0] *= invS;
@@ -1714,8 +1692,6 @@ SPHX_HD void momentumEnergyJLoop(unsigned i, const SphConsts& sc, const G& box, 
         e1 += mja * Wi * vui;
         e2 += av * Wi * vui + bv * Wj * vuj;
     });
-    reduceAcross(ld, mx, my, mz, e1, e2);
-    reduceAcrossMax(ld, maxvs);
     HT aviscE     = smax(HT(0), HT(-0.5) * e2);
     HT Kf         = HT(sc.K) / kf.wqScale(); // (every summed term carries one S-scaled kernel value)
     duOut         = double(Kf * (-prhoi * e1 + HT(0.5) * aviscE));

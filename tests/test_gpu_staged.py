@@ -1,70 +1,12 @@
-"""LDS-staged pair loops (csrc/hip/staged.h) against the per-lane-gather loops on the same inputs: every VE step field
-after two steps of a case, fp32 summation-order tolerance (the staged loops add W partial sums per target).
-
-The windowed path (a group's source union larger than the LDS capacity or spread over more than 63 chunk slots) is
-forced with a neighbor count of ~300 (unions of ~2,000 sources)."""
+"""The packed neighbor lists as the LDS-staged pair loops (csrc/hip/staged.h) read them. The loops themselves are
+compared with the gathered loops, bit for bit, in test_gpu_staged_block.py and test_gpu_staged_block_xg.py."""
 
 import pytest
-import torch
 
 from sphexa_amd.app.simulation import Simulation
 from sphexa_amd.ops import _lib
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("x", "y", "z", "vx", "vy", "vz", "h", "temp", "u", "alpha", "xm", "kx", "du", "c", "nc")
-
-
-def _run(gpu, case, n, mask, steps=2, ng=None):
-    hp = _lib.hip()
-    old = hp.staged_mask()
-    hp.set_staged(mask)
-    try:
-        sim = Simulation(case, n=n, device=gpu)
-        if ng is not None:
-            # ~ng0 neighbors from the first search on: h scaled from the case's 100-neighbor value
-            sim.d.ng0, sim.d.ngmax = ng
-            sim.d["h"] = sim.d["h"] * (ng[0] / 100.0) ** (1.0 / 3.0)
-        sim.run(steps)
-        torch.cuda.synchronize()
-        out = {}
-        for f in FIELDS:
-            try:
-                v = sim.local(f)
-            except Exception:  # (fields a case does not allocate)
-                continue
-            if v is not None and v.numel():
-                out[f] = v.double().cpu()
-        return out
-    finally:
-        hp.set_staged(old)
-
-
-def _compare(a, b, tol):
-    assert a.keys() == b.keys() and "x" in a
-    worst = {}
-    for f in a:
-        scale = float(a[f].abs().max()) or 1.0
-        err = float((a[f] - b[f]).abs().max()) / scale
-        worst[f] = err
-        assert torch.isfinite(b[f]).all(), f
-    bad = {f: e for f, e in worst.items() if e > tol}
-    assert not bad, f"staged vs gathered: {bad} (all: {worst})"
-
-
-@pytest.mark.parametrize("case,n,mask", [("sedov", 24, 1), ("sedov", 24, 31), ("noh", 24, 31), ("evrard", 24, 31)])
-def test_staged_loops_match_gathered(gpu, case, n, mask):
-    a = _run(gpu, case, n, 0)
-    b = _run(gpu, case, n, mask)
-    _compare(a, b, 2e-5)
-
-
-def test_staged_windows_match_gathered(gpu):
-    """~300 neighbors per particle: most groups need several LDS windows"""
-    a = _run(gpu, "sedov", 20, 0, steps=1, ng=(300, 400))
-    b = _run(gpu, "sedov", 20, 31, steps=1, ng=(300, 400))
-    assert float(a["nc"].mean()) > 250
-    _compare(a, b, 2e-5)
 
 
 def test_search_masks_cover_every_code(gpu):
