@@ -5,7 +5,8 @@
     sim.d["rho"], sim.domain.start_index(), ...
 
 ``ewald=S`` (S > 0) makes the self-gravity of a fully periodic cubic box periodic: S shells of replicas are walked
-explicitly and every farther image comes from the Ewald sum of the root multipole (single rank).
+explicitly and every farther image comes from the Ewald sum of the root multipole. It runs on any number of ranks
+(``comm``): each rank evaluates its local tree and the remote multipoles it received in one pass.
 
 Parity: reference main/src/sphexa/sphexa.cpp:104-200 (initializer -> propagator -> domain -> sync -> time loop).
 The global bucket size follows the reference: max(bucketSizeFocus, N / (100 * numRanks)).
@@ -29,7 +30,8 @@ from ..ops import _lib
 
 
 def check_ewald(shells: int, G: float, box, num_ranks: int):
-    """the conditions of periodic (Ewald) self-gravity; raises ValueError when one does not hold"""
+    """the conditions of periodic (Ewald) self-gravity; raises ValueError when one does not hold (any number of
+    ranks is fine)"""
     from ..utils.box import PERIODIC
 
     if shells < 0:
@@ -41,8 +43,6 @@ def check_ewald(shells: int, G: float, box, num_ranks: int):
     L = box.hi[0] - box.lo[0]
     if any(abs((box.hi[k] - box.lo[k]) - L) > 1e-12 * L for k in range(3)):
         raise ValueError("Ewald gravity needs a cubic box")
-    if num_ranks > 1:
-        raise ValueError("Ewald gravity runs on a single rank only")
 
 
 class Simulation:

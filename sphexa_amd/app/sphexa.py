@@ -39,9 +39,9 @@ Where possible options are:
     --glass FILE        Use glass block as template to generate initial x,y,z configuration (built-in otherwise)
     --theta NUM         Gravity accuracy parameter [default 0.5 when self-gravity is active]
     --G NUM             Gravitational constant [default dependent on test case]
-    --ewald [S]         Periodic self-gravity (fully periodic cubic box, one rank): S shells of replicas walked
-                        explicitly [1], farther images by Ewald summation. A run option: not stored in snapshots,
-                        give it again when restarting from a file
+    --ewald [S]         Periodic self-gravity (fully periodic cubic box, any number of ranks): S shells of replicas
+                        walked explicitly [1], farther images by Ewald summation. A run option: not stored in
+                        snapshots, give it again when restarting from a file
     --prop STRING       Choice of SPH propagator [default: modern SPH]. For standard SPH, use "std"
     -s NUM              NUM Number of iterations (time-steps) [200] or simulation time if NUM is not integral
     -w NUM              Dump particle data every NUM iterations (time-steps) [-1]

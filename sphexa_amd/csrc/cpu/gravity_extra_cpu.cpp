@@ -9,6 +9,12 @@
  * target point; the monopole of every farther image comes from the Ewald lattice sum of the root mass (minus the
  * images already counted), the quadrupole of the images S < |n|_inf <= S + 2 from explicit M2P (it falls off as
  * r^-4). directEwald() is the O(N^2) Ewald oracle. Cubic boxes only (as in the reference).
+ *
+ * Several ranks: the sources of a rank are its local tree (own particles and gravity halos) and the tree over the
+ * multipoles received through the locally-essential-tree exchange (no particles, leaves always accepted). The
+ * periodic potential is linear in the sources, so the replicas of both trees are walked and each root gets its own
+ * lattice correction; the sender marked its nodes with the minimum image, so a received multipole is far enough for
+ * every replica.
  */
 #include <algorithm>
 #include <cmath>
@@ -94,7 +100,11 @@ struct Ewald
     }
 };
 
-//! @brief Barnes-Hut of the whole tree evaluated at point (px, py, pz) for target particle i (softening h_i)
+/*! @brief Barnes-Hut of the whole tree evaluated at point (px, py, pz) for target particle i (softening h_i)
+ *
+ * @tparam Particles  false: the tree over received multipoles, whose leaves hold no particles on this rank
+ */
+template<bool Particles>
 static void bhPoint(double px, double py, double pz, double hi, const int32_t* child, const int32_t* n2l,
                     const int32_t* ns, const int32_t* ne, const double* centers, const Quadrupole* mp,
                     const double* x, const double* y, const double* z, const float* h, const float* m,
@@ -114,8 +124,9 @@ static void bhPoint(double px, double py, double pz, double hi, const int32_t* c
         }
         else if (n2l[node] >= 0)
         {
-            for (int32_t j = ns[node]; j < ne[node]; ++j)
-                p2p(x[j] - px, y[j] - py, z[j] - pz, double(m[j]), hi, double(h[j]), acc);
+            if constexpr (Particles)
+                for (int32_t j = ns[node]; j < ne[node]; ++j)
+                    p2p(x[j] - px, y[j] - py, z[j] - pz, double(m[j]), hi, double(h[j]), acc);
         }
         else
         {
@@ -126,17 +137,66 @@ static void bhPoint(double px, double py, double pz, double hi, const int32_t* c
     }
 }
 
-double computeGravityEwald(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
-                           const int32_t* ne, const double* centers, const Quadrupole* mp, const double* x,
-                           const double* y, const double* z, const float* h, const float* m, double G, double L,
-                           int numShells, float* ax, float* ay, float* az, double* ugrav)
+//! @brief a source tree of computeGravityEwald: structure, mass centers + MAC radii, quadrupoles
+struct EwaldTree
+{
+    const int32_t *child, *n2l, *ns, *ne;
+    const double* centers;
+    const Quadrupole* mp;
+};
+
+/*! @brief far field of one tree beyond its explicit replicas, added to acc: M psi and M grad psi of the root mass
+ *  about the root's mass center minus the (2S+1)^3 explicit images, the trace term, and the quadrupole-only images
+ *  S < |n|_inf <= S + 2
+ */
+static void ewaldRootCorrection(const Ewald& ew, const double* rc, const Quadrupole& root, double xi, double yi,
+                                double zi, double L, int S, double acc[4])
+{
+    const double M   = root.q[qMass];
+    Quadrupole qOnly = root;
+    qOnly.q[qMass]   = 0; // far-image quadrupole terms only; their monopoles are in the Ewald sum
+    const int S2     = S + 2;
+    // monopoles of all images beyond the explicit shells: Ewald sum minus the explicit images
+    double r[3] = {xi - rc[0], yi - rc[1], zi - rc[2]};
+    double p, g[3];
+    ew.psi(r, p, g);
+    for (int a = -S; a <= S; ++a)
+        for (int b = -S; b <= S; ++b)
+            for (int c = -S; c <= S; ++c)
+            {
+                double s[3] = {r[0] + a * L, r[1] + b * L, r[2] + c * L};
+                double d2   = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+                double id   = 1.0 / std::sqrt(d2);
+                p -= id;
+                for (int d = 0; d < 3; ++d)
+                    g[d] += s[d] * id * id * id;
+            }
+    acc[0] -= M * p;
+    for (int d = 0; d < 3; ++d)
+        acc[1 + d] += M * g[d];
+    // second-moment (trace) term of the far field: unlike 1/r, the image sum has a nonzero Laplacian
+    // (neutralizing background, 4 pi / V), so sum_j m_j psi_far(x_i - x_j) = M psi_far(r) +
+    // (2 pi / 3V) sum_j m_j |x_j - com|^2 + traceless terms; a constant in x_i (no force)
+    acc[0] -= 2.0 * M_PI / (3.0 * L * L * L) * double(root.q[qTrace]);
+    // quadrupoles of the next two shells of images
+    for (int a = -S2; a <= S2; ++a)
+        for (int b = -S2; b <= S2; ++b)
+            for (int c = -S2; c <= S2; ++c)
+            {
+                if (std::max({std::abs(a), std::abs(b), std::abs(c)}) <= S) continue;
+                m2p(r[0] - a * L, r[1] - b * L, r[2] - c * L, qOnly, acc);
+            }
+}
+
+/*! @brief periodic gravity of targets [first, last) from the local tree and, if @p remote is given (a tree with
+ *  nodes), from the tree over the received multipoles; returns the rank-local 0.5 G sum m phi
+ */
+double computeGravityEwald(int64_t first, int64_t last, const EwaldTree& local, const EwaldTree* remote,
+                           const double* x, const double* y, const double* z, const float* h, const float* m,
+                           double G, double L, int numShells, float* ax, float* ay, float* az, double* ugrav)
 {
     const Ewald ew{L, 2.0 / L, 2, 5};
-    const double* rc = centers; // root: mass center + total mass
-    const double M   = mp[0].q[qMass];
-    Quadrupole qOnly = mp[0];
-    qOnly.q[qMass]   = 0; // far-image quadrupole terms only; their monopoles are in the Ewald sum
-    const int S = numShells, S2 = numShells + 2;
+    const int S = numShells;
     double utot = 0;
 #pragma omp parallel for schedule(dynamic, 8) reduction(+ : utot)
     for (int64_t i = first; i < last; ++i)
@@ -145,38 +205,17 @@ double computeGravityEwald(int64_t first, int64_t last, const int32_t* child, co
         for (int a = -S; a <= S; ++a)
             for (int b = -S; b <= S; ++b)
                 for (int c = -S; c <= S; ++c)
-                    bhPoint(x[i] - a * L, y[i] - b * L, z[i] - c * L, h[i], child, n2l, ns, ne, centers, mp, x, y,
-                            z, h, m, acc);
-        // monopoles of all images beyond the explicit shells: Ewald sum minus the explicit images
-        double r[3] = {x[i] - rc[0], y[i] - rc[1], z[i] - rc[2]};
-        double p, g[3];
-        ew.psi(r, p, g);
-        for (int a = -S; a <= S; ++a)
-            for (int b = -S; b <= S; ++b)
-                for (int c = -S; c <= S; ++c)
                 {
-                    double s[3] = {r[0] + a * L, r[1] + b * L, r[2] + c * L};
-                    double d2   = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
-                    double id   = 1.0 / std::sqrt(d2);
-                    p -= id;
-                    for (int d = 0; d < 3; ++d)
-                        g[d] += s[d] * id * id * id;
+                    const double px = x[i] - a * L, py = y[i] - b * L, pz = z[i] - c * L;
+                    bhPoint<true>(px, py, pz, h[i], local.child, local.n2l, local.ns, local.ne, local.centers,
+                                  local.mp, x, y, z, h, m, acc);
+                    if (remote)
+                        bhPoint<false>(px, py, pz, h[i], remote->child, remote->n2l, remote->ns, remote->ne,
+                                       remote->centers, remote->mp, x, y, z, h, m, acc);
                 }
-        acc[0] -= M * p;
-        for (int d = 0; d < 3; ++d)
-            acc[1 + d] += M * g[d];
-        // second-moment (trace) term of the far field: unlike 1/r, the image sum has a nonzero Laplacian
-        // (neutralizing background, 4 pi / V), so sum_j m_j psi_far(x_i - x_j) = M psi_far(r) +
-        // (2 pi / 3V) sum_j m_j |x_j - com|^2 + traceless terms; a constant in x_i (no force)
-        acc[0] -= 2.0 * M_PI / (3.0 * L * L * L) * double(mp[0].q[qTrace]);
-        // quadrupoles of the next two shells of images
-        for (int a = -S2; a <= S2; ++a)
-            for (int b = -S2; b <= S2; ++b)
-                for (int c = -S2; c <= S2; ++c)
-                {
-                    if (std::max({std::abs(a), std::abs(b), std::abs(c)}) <= S) continue;
-                    m2p(r[0] - a * L, r[1] - b * L, r[2] - c * L, qOnly, acc);
-                }
+        // root: mass center + total mass
+        ewaldRootCorrection(ew, local.centers, local.mp[0], x[i], y[i], z[i], L, S, acc);
+        if (remote) ewaldRootCorrection(ew, remote->centers, remote->mp[0], x[i], y[i], z[i], L, S, acc);
         double u = G * m[i] * acc[0];
         utot += u;
         if (ugrav) ugrav[i] += u;
@@ -248,13 +287,22 @@ void bindGravityExtra(py::module& m)
 {
     m.def("compute_gravity_ewald",
           [](int64_t first, int64_t last, Ptr child, Ptr n2l, Ptr ns, Ptr ne, Ptr centers, Ptr mp, Ptr x, Ptr y,
-             Ptr z, Ptr h, Ptr mm, double G, double L, int shells, Ptr ax, Ptr ay, Ptr az, Ptr ugrav)
+             Ptr z, Ptr h, Ptr mm, double G, double L, int shells, Ptr ax, Ptr ay, Ptr az, Ptr ugrav,
+             int64_t rnodes, Ptr rchild, Ptr rn2l, Ptr rns, Ptr rne, Ptr rcenters, Ptr rmp)
           {
-              return computeGravityEwald(first, last, P<int32_t>(child), P<int32_t>(n2l), P<int32_t>(ns),
-                                         P<int32_t>(ne), P<double>(centers), P<Quadrupole>(mp), P<double>(x),
+              const EwaldTree local{P<int32_t>(child), P<int32_t>(n2l),    P<int32_t>(ns),
+                                    P<int32_t>(ne),    P<double>(centers), P<Quadrupole>(mp)};
+              const EwaldTree remote{P<int32_t>(rchild), P<int32_t>(rn2l),    P<int32_t>(rns),
+                                     P<int32_t>(rne),    P<double>(rcenters), P<Quadrupole>(rmp)};
+              return computeGravityEwald(first, last, local, rnodes > 0 ? &remote : nullptr, P<double>(x),
                                          P<double>(y), P<double>(z), P<float>(h), P<float>(mm), G, L, shells,
                                          P<float>(ax), P<float>(ay), P<float>(az), P<double>(ugrav));
-          });
+          },
+          py::arg("first"), py::arg("last"), py::arg("child"), py::arg("n2l"), py::arg("ns"), py::arg("ne"),
+          py::arg("centers"), py::arg("mp"), py::arg("x"), py::arg("y"), py::arg("z"), py::arg("h"), py::arg("m"),
+          py::arg("G"), py::arg("L"), py::arg("shells"), py::arg("ax"), py::arg("ay"), py::arg("az"),
+          py::arg("ugrav"), py::arg("rnodes") = 0, py::arg("rchild") = 0, py::arg("rn2l") = 0, py::arg("rns") = 0,
+          py::arg("rne") = 0, py::arg("rcenters") = 0, py::arg("rmp") = 0);
     m.def("direct_ewald",
           [](int64_t n, Ptr x, Ptr y, Ptr z, Ptr mm, double G, double L, Ptr ax, Ptr ay, Ptr az)
           {

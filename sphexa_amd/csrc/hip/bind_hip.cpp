@@ -545,14 +545,21 @@ PYBIND11_MODULE(_sphx_hip, m)
     m.def("compute_gravity_ewald",
           [](int64_t first, int64_t last, Ptr child, Ptr n2l, Ptr ns, Ptr ne, Ptr centers, Ptr mp, Ptr x, Ptr y,
              Ptr z, Ptr h, Ptr mm, double G, double L, int shells, Ptr ktable, Ptr sums, Ptr ax, Ptr ay, Ptr az,
-             Ptr ugrav, Ptr esum, Ptr overflow, Ptr s)
+             Ptr ugrav, Ptr esum, Ptr overflow, Ptr s, int64_t rnodes, Ptr rchild, Ptr rn2l, Ptr rcenters, Ptr rmp)
           {
               computeGravityEwald(first, last, P<int32_t>(child), P<int32_t>(n2l), P<int32_t>(ns), P<int32_t>(ne),
-                                  P<double>(centers), P<void>(mp), P<double>(x), P<double>(y), P<double>(z),
+                                  P<double>(centers), P<void>(mp), rnodes, P<int32_t>(rchild), P<int32_t>(rn2l),
+                                  P<double>(rcenters), P<void>(rmp), P<double>(x), P<double>(y), P<double>(z),
                                   P<float>(h), P<float>(mm), G, L, shells, P<double>(ktable), P<double>(sums),
                                   P<float>(ax), P<float>(ay), P<float>(az), P<double>(ugrav), P<double>(esum),
                                   P<int>(overflow), St(s));
-          });
+          },
+          py::arg("first"), py::arg("last"), py::arg("child"), py::arg("n2l"), py::arg("ns"), py::arg("ne"),
+          py::arg("centers"), py::arg("mp"), py::arg("x"), py::arg("y"), py::arg("z"), py::arg("h"), py::arg("m"),
+          py::arg("G"), py::arg("L"), py::arg("shells"), py::arg("ktable"), py::arg("sums"), py::arg("ax"),
+          py::arg("ay"), py::arg("az"), py::arg("ugrav"), py::arg("esum"), py::arg("overflow"), py::arg("stream"),
+          py::arg("rnodes") = 0, py::arg("rchild") = 0, py::arg("rn2l") = 0, py::arg("rcenters") = 0,
+          py::arg("rmp") = 0);
     m.def("ewald_ktable", [](double L) { return ewaldKTableHost(L); },
           "k-space coefficient table of a cubic box of length L (sphx/ewald.hpp ewaldKTable)");
     // ---------------------------------------------------------------------------------------------- cooling

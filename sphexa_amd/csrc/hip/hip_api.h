@@ -290,12 +290,14 @@ void computeGravityMultipole(int order, int64_t first, int64_t last, const int32
                              hipStream_t s);
 
 // ewald.hip (periodic self-gravity of a cubic box; math: sphx/ewald.hpp)
-//! ktable: ewaldKTableHost(L) copied to the device; sums: 4 (last - first) doubles of scratch
+//! ktable: ewaldKTableHost(L) copied to the device; sums: 4 (last - first) doubles of scratch; r*: the tree over the
+//! multipoles received from other ranks (rnodes nodes, 0: none), walked and lattice-corrected in the same two launches
 void computeGravityEwald(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
-                         const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
-                         const double* z, const float* h, const float* m, double G, double L, int numShells,
-                         const double* ktable, double* sums, float* ax, float* ay, float* az, double* ugrav,
-                         double* esum, int* overflow, hipStream_t s);
+                         const int32_t* ne, const double* centers, const void* mp, int64_t rnodes,
+                         const int32_t* rchild, const int32_t* rn2l, const double* rcenters, const void* rmp,
+                         const double* x, const double* y, const double* z, const float* h, const float* m, double G,
+                         double L, int numShells, const double* ktable, double* sums, float* ax, float* ay, float* az,
+                         double* ugrav, double* esum, int* overflow, hipStream_t s);
 std::vector<double> ewaldKTableHost(double L);
 
 // gravity.hip

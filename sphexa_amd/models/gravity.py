@@ -91,15 +91,19 @@ class MultipoleHolder:
 
     def traverse_ewald(self, d, domain, shells: int):
         """periodic self-gravity of a cubic box (ops.gravity.compute_gravity_ewald: ``shells`` of replicas walked
-        explicitly, the farther images through the Ewald sum of the root multipole), single rank. The energy comes
-        to the host with the call: nothing stays pending"""
+        explicitly, the farther images through the Ewald sum of the root multipole). On several ranks the sources
+        are the local tree (own particles and gravity halos) and the remote LET tree, in the same evaluation; a rank
+        that received no multipoles evaluates its local tree only. The remote tree is built here, on the current
+        stream, like in ``traverse``. The rank's share of the energy comes to the host with the call: nothing stays
+        pending"""
         self.finish_sync(d)
         self._rstats = None
         self.pending = []
+        remote = getattr(domain, "remote_tree", None) if domain.size > 1 else None
         self._host_energy = G.compute_gravity_ewald(domain.octree, self.centers, self.multipoles,
                                                     domain.start_index(), domain.end_index(), d["x"], d["y"], d["z"],
                                                     d["h"], d["m"], d.g, domain.box, d["ax"], d["ay"], d["az"],
-                                                    shells=shells)
+                                                    shells=shells, remote=remote)
         self._finalize(d, [])
 
     def finish(self, d, host_vals):

@@ -62,7 +62,8 @@ class Propagator:
     # propagators that use the new dt on the host within the step (stirring, cooling) never defer
     needs_host_dt = False
     # periodic self-gravity: > 0 evaluates gravity with this many shells of explicit replicas plus the Ewald lattice
-    # sum (MultipoleHolder.traverse_ewald) on the plain path of _gravity: no side streams, no deferred energy
+    # sum (MultipoleHolder.traverse_ewald, any number of ranks) on the plain path of _gravity: no side streams, no
+    # deferred energy
     ewald_shells = 0
 
     def __init__(self, out=sys.stdout, rank: int = 0, quiet: bool = False):

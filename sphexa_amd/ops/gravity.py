@@ -530,12 +530,15 @@ def _ewald_ktable(L: float, device) -> torch.Tensor:
 
 
 def compute_gravity_ewald(tree: Octree, centers, mp, first: int, last: int, x, y, z, h, m, G: float, box: Box,
-                          ax, ay, az, shells: int = 1, ugrav=None) -> float:
+                          ax, ay, az, shells: int = 1, ugrav=None, remote=None) -> float:
     """periodic self-gravity (cubic box): Barnes-Hut over the central box and ``shells`` of replicas plus the Ewald
     lattice sum of the root multipole for all farther images (reference nbody/traversal_ewald_cpu.hpp, CPU-only
     there). Adds G * a to ax, ay, az for targets [first, last) and the per-particle energy to ``ugrav``; returns
-    0.5 * sum G m phi. Device tensors: csrc/hip/ewald.hip on the current stream (one host copy: the energy and the
-    overflow flag)."""
+    this rank's 0.5 * sum G m phi. ``remote``: (octree, centers, quadrupoles) over the multipoles received from the
+    other ranks (``remote_let_tree``); its replicas are walked with the local tree's and its root gets a lattice
+    correction of its own (the potential is linear in the sources). None or a tree without nodes: the local tree
+    only. Device tensors: csrc/hip/ewald.hip on the current stream, with or without a remote tree one traversal
+    launch, one lattice launch and one host copy (the energy and the overflow flag)."""
     L = box.hi[0] - box.lo[0]
     if any(abs((box.hi[d] - box.lo[d]) - L) > 1e-12 * L for d in range(3)):
         raise ValueError("Ewald gravity needs a cubic box")
@@ -545,18 +548,29 @@ def compute_gravity_ewald(tree: Octree, centers, mp, first: int, last: int, x, y
             tree.node_end.data_ptr(), centers.data_ptr(), mp.data_ptr(), x.data_ptr(), y.data_ptr(), z.data_ptr(),
             h.data_ptr(), m.data_ptr(), float(G), float(L), int(shells))
     out = (ax.data_ptr(), ay.data_ptr(), az.data_ptr(), 0 if ugrav is None else ugrav.data_ptr())
+    rargs = {}
+    if remote is not None and remote[0].num_nodes > 0:
+        rt, rc, rmp = remote
+        if rc.device != x.device or rmp.device != x.device:
+            raise ValueError("Ewald gravity: the remote tree is not on the particles' device")
+        if rc.numel() < 4 * rt.num_nodes or rmp.numel() < 8 * rt.num_nodes or rmp.dtype != torch.float32:
+            raise ValueError("Ewald gravity: remote centers/quadrupoles do not match the remote tree")
+        rargs = dict(rnodes=int(rt.num_nodes), rchild=rt.child_offsets.data_ptr(), rn2l=rt.node_to_leaf.data_ptr(),
+                     rcenters=rc.data_ptr(), rmp=rmp.data_ptr())
     if x.is_cuda:
         ktable = _ewald_ktable(L, x.device)
         sums = torch.empty(4 * (last - first), dtype=torch.float64, device=x.device)
         # [energy (float64), overflow count (as an int32 in the second word)]: one fill, one copy to the host
         res = zero_(torch.empty(2, dtype=torch.float64, device=x.device))
         _lib.hip().compute_gravity_ewald(first, last, *args, ktable.data_ptr(), sums.data_ptr(), *out,
-                                         res.data_ptr(), res[1:].data_ptr(), _stream())
+                                         res.data_ptr(), res[1:].data_ptr(), _stream(), **rargs)
         host = res.cpu()
         if int(host.view(torch.int32)[2]) != 0:
             raise RuntimeError("Ewald traversal stack overflow")
         return float(host[0])
-    return float(_lib.cpu().compute_gravity_ewald(first, last, *args, *out))
+    if rargs:
+        rargs.update(rns=remote[0].node_start.data_ptr(), rne=remote[0].node_end.data_ptr())
+    return float(_lib.cpu().compute_gravity_ewald(first, last, *args, *out, **rargs))
 
 
 def direct_ewald(x, y, z, m, G: float, L: float):
