@@ -626,6 +626,18 @@ PYBIND11_MODULE(_sphx_hip, m)
           py::arg("nsrc"), py::arg("num_nodes"), py::arg("rec"), py::arg("mm"), py::arg("stream"),
           py::arg("phase") = 0);
     m.def("gravity_scratch_bytes", [](int64_t n, int capM, int capL) { return gravityScratchBytes(n, capM, capL); });
+    m.def("gravity_scratch_layout",
+          [](int64_t n, int capM, int capL)
+          {
+              const std::vector<int64_t> v = gravityScratchLayout(n, capM, capL);
+              py::dict d;
+              const char* names[] = {"spillList", "counts", "pcount", "mlist", "llist", "tag_shift", "id_mask", "stack"};
+              for (size_t i = 0; i < v.size(); ++i)
+                  d[names[i]] = v[i];
+              return d;
+          },
+          "int32-word offsets of the interaction-list slabs in the gravity scratch, the entry tag constants and the\n"
+          "capacity of the list kernel's traversal stack");
     m.def("device_checks_enabled", &deviceChecksEnabled);
     m.def("device_check_flags", []() { return dcheckHydro() | dcheckSfc() | dcheckGravity(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");

@@ -1869,6 +1869,20 @@ static GravScratch carve(void* scratch, int64_t groups, int capM, int capL)
     return c;
 }
 
+//! @brief int32-word offsets of {spillList, counts, pcount, mlist, llist} in the scratch of an evaluation of n targets
+//!        (tests read the interaction-list slabs through them), followed by the entry tag constants {kTagShift, kIdMask}
+//!        and the capacity of the list kernel's LDS traversal stack {kGStack}
+std::vector<int64_t> gravityScratchLayout(int64_t n, int capM, int capL)
+{
+    int64_t groups = (n + 63) / 64;
+    // carve() only adds offsets to its base: a one-word array stands in for the scratch, no carved pointer is read
+    static int32_t origin[1];
+    const GravScratch c = carve(origin, groups, capM, capL);
+    auto words = [&](const int32_t* p) { return int64_t((uintptr_t(p) - uintptr_t(origin)) / sizeof(int32_t)); };
+    return {words(c.spillList), words(c.S.counts), words(c.S.pcount), words(c.S.mlist), words(c.S.llist),
+            int64_t(kTagShift), int64_t(kIdMask), int64_t(kGStack)};
+}
+
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
                          const double* z, unsigned long long* stats, void* scratch, int testFrontCap, int capM,

@@ -314,6 +314,8 @@ void gravitySetMac(int64_t N, const KeyT* prefixes, const Box& box, int kind, do
 // Barnes-Hut in two phases: interaction lists (per 64-target group, tagged with the target halves they apply to),
 // then evaluation (M2P kernel, P2P kernel, combine, fused fallback for groups that overflowed the slabs)
 size_t gravityScratchBytes(int64_t n, int capM, int capL);
+// int32-word offsets of {spillList, counts, pcount, mlist, llist} in that scratch, then {kTagShift, kIdMask, kGStack}
+std::vector<int64_t> gravityScratchLayout(int64_t n, int capM, int capL);
 
 // device-check build (common.h SPHX_DCHECK): read and clear the failed-check bits of each translation unit
 unsigned dcheckHydro();
