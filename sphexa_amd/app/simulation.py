@@ -45,16 +45,31 @@ def check_ewald(shells: int, G: float, box, num_ranks: int):
         raise ValueError("Ewald gravity needs a cubic box")
 
 
+def check_multipole_order(order: int, device, num_ranks: int, ewald: int):
+    """the conditions of an order-P far field (``multipole_order``); raises ValueError when one does not hold"""
+    if not 1 <= order <= 6:
+        raise ValueError("multipole order must be in [1, 6] (0: quadrupoles)")
+    if num_ranks > 1:
+        raise ValueError("an order-P far field runs on one rank only (the multipole exchange ships quadrupoles)")
+    if ewald:
+        raise ValueError("an order-P far field cannot be combined with Ewald (periodic) gravity")
+    if torch.device(device).type != "cuda":
+        raise ValueError("an order-P far field in a simulation needs the GPU")
+
+
 class Simulation:
     def __init__(self, init: str, n: int = 50, prop: str = "ve", device=None, glass=None, av_clean=False,
                  comm: Comm | None = None, theta: float | None = None, G: float | None = None, out=None,
-                 quiet=True, bucket_size_focus: int | None = None, initializer=None, ewald: int = 0):
+                 quiet=True, bucket_size_focus: int | None = None, initializer=None, ewald: int = 0,
+                 multipole_order: int = 0):
         self.comm = comm or Comm()
         rank, size = self.comm.rank, self.comm.size
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
         self.init_name = init
+        if multipole_order:
+            check_multipole_order(int(multipole_order), self.device, size, int(ewald))
         self.sim_init = initializer if initializer is not None else initializer_factory(init, glass)
         self.propagator = propagator_factory(prop, av_clean, out, rank, quiet, self.sim_init.constants())
         self.d = P.ParticlesData(self.device)
@@ -69,6 +84,7 @@ class Simulation:
         if ewald:
             check_ewald(int(ewald), self.d.g, box, size)
             self.propagator.ewald_shells = int(ewald)
+        self.propagator.multipole_order = int(multipole_order)
         # (tuning: SPHX_BUCKET_FOCUS overrides the local octree's leaf capacity, reference bucketSizeFocus = 64)
         # (an explicit argument wins over the environment)
         if bucket_size_focus is None:

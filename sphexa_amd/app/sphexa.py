@@ -42,6 +42,8 @@ Where possible options are:
     --ewald [S]         Periodic self-gravity (fully periodic cubic box, any number of ranks): S shells of replicas
                         walked explicitly [1], farther images by Ewald summation. A run option: not stored in
                         snapshots, give it again when restarting from a file
+    --multipole-order P Far field of the self-gravity as Cartesian multipoles of order P = 1..6 [quadrupoles] over the
+                        same interaction lists (GPU, one rank, not with --ewald): accuracy without lowering --theta
     --prop STRING       Choice of SPH propagator [default: modern SPH]. For standard SPH, use "std"
     -s NUM              NUM Number of iterations (time-steps) [200] or simulation time if NUM is not integral
     -w NUM              Dump particle data every NUM iterations (time-steps) [-1]
@@ -135,6 +137,12 @@ def main(argv=None) -> int:
         shells = int(parser.get("--ewald", 1))
         check_ewald(shells, d.g, box, num_ranks)
         propagator.ewald_shells = shells
+    if parser.exists("--multipole-order"):
+        from .simulation import check_multipole_order
+
+        order = int(parser.get("--multipole-order", 4))
+        check_multipole_order(order, device, num_ranks, propagator.ewald_shells)
+        propagator.multipole_order = order
 
     if not parser.exists("-o"):
         out_file += writer.suffix

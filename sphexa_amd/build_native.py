@@ -112,6 +112,11 @@ def build_cpu(verbose=False, sanitize=False):
     return target
 
 
+# per-source flags of the HIP module. gravity_order.hip: no packed fp32 VALU instructions (its pair arithmetic is
+# written on scalars; the compiler's own v_pk_*_f32 pairing of independent chains costs operand moves, as above)
+HIP_SOURCE_FLAGS = {"gravity_order.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_hip(verbose=False, variant=None, defines=()):
     """``variant``/``defines``: tuning build into _native/variants/<variant>/ with extra -D flags (loaded when
     SPHX_HIP_VARIANT=<variant> is set)"""
@@ -136,7 +141,8 @@ def build_hip(verbose=False, variant=None, defines=()):
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
             lang = ["-x", "hip"] if s.endswith(".hip") else []
-            jobs.append(([hipcc, *flags, *lang, "-c", s, "-o", o], o))
+            extra = HIP_SOURCE_FLAGS.get(os.path.basename(s), [])
+            jobs.append(([hipcc, *flags, *extra, *lang, "-c", s, "-o", o], o))
     _compile_all(jobs, verbose)
     if jobs or _newer(target, objs):
         # link to a temporary name and rename: a concurrent reader (a repository snapshot, a running test) sees the

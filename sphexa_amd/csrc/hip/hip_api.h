@@ -2,6 +2,8 @@
 #pragma once
 
 #include <cstdint>
+#include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -283,11 +285,21 @@ void coolingEos(int64_t first, int64_t last, double gamma, const float* rho, con
 void multipoleUpsweep(int order, int64_t N, const int32_t* n2l, const int32_t* child, const int64_t* levelRange,
                       const int32_t* ns, const int32_t* ne, const double* x, const double* y, const double* z,
                       const float* m, const double* centers, float* Q, hipStream_t s);
-void computeGravityMultipole(int order, int64_t first, int64_t last, const int32_t* child, const int32_t* n2l,
-                             const int32_t* ns, const int32_t* ne, const double* centers, const float* Q,
-                             const double* x, const double* y, const double* z, const float* h, const float* m,
-                             double G, float* ax, float* ay, float* az, double* ugrav, double* esum, int* overflow,
-                             hipStream_t s);
+//! @brief call f with the expansion order as a compile-time constant (multipole.hip, gravity_order.hip)
+template<class F>
+void withOrder(int P, F&& f)
+{
+    switch (P)
+    {
+        case 1: f(std::integral_constant<int, 1>{}); return;
+        case 2: f(std::integral_constant<int, 2>{}); return;
+        case 3: f(std::integral_constant<int, 3>{}); return;
+        case 4: f(std::integral_constant<int, 4>{}); return;
+        case 5: f(std::integral_constant<int, 5>{}); return;
+        case 6: f(std::integral_constant<int, 6>{}); return;
+    }
+    throw std::invalid_argument("GPU multipole order must be in [1, 6]");
+}
 
 // ewald.hip (periodic self-gravity of a cubic box; math: sphx/ewald.hpp)
 //! ktable: ewaldKTableHost(L) copied to the device; sums: 4 (last - first) doubles of scratch; r*: the tree over the
@@ -330,9 +342,12 @@ void computeGravityEval(int64_t first, int64_t last, const int32_t* child, const
                         const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
                         const double* z, const float* h, const float* m, float G, float* ax, float* ay, float* az,
                         double* ugrav, double* out, unsigned long long* stats, void* scratch, int capM, int capL,
-                        void* pacc, int64_t nsrc, int64_t numNodes, void* rec, const double* mm, hipStream_t s, int phase = 0);
-//! bytes of the record buffer of computeGravityEval (16 B per source particle, 40 B per tree node)
-inline size_t gravityRecordBytes(int64_t nsrc, int64_t numNodes) { return size_t(16 * nsrc + 40 * numNodes); }
+                        void* pacc, int64_t nsrc, int64_t numNodes, void* rec, const double* mm, hipStream_t s, int phase = 0,
+                        int order = 0, const float* Q = nullptr);
+//! bytes per tree node of the record buffer of computeGravityEval (after 16 B per source particle): 40 B at order 0
+//! (quadrupoles), else the order-P record of gravity_order.hip
+size_t gravityOrderRecordBytes(int order);
+inline size_t gravityNodeRecordBytes(int order) { return order > 0 ? gravityOrderRecordBytes(order) : 40; }
 void directSum(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
                const float* h, const float* m, float G, float* ax, float* ay, float* az, double* ugrav, double* out,
                hipStream_t s);

@@ -20,7 +20,12 @@ from ..parallel.comm import SUM
 
 
 class MultipoleHolder:
-    def __init__(self):
+    """``order`` P > 0 (GPU, one rank): the far field is the order-P expansion of the Cartesian moments
+    (ops.gravity.multipole_upsweep) over the same interaction lists; 0: quadrupoles"""
+
+    def __init__(self, order: int = 0):
+        self.order = int(order)
+        self.moments = None
         self.centers = None
         self.multipoles = None
         self.stats = {}
@@ -32,6 +37,11 @@ class MultipoleHolder:
         ot = domain.octree
         self.centers, self.multipoles = G.upsweep(ot, d["x"], d["y"], d["z"], d["m"], domain.box, domain.theta,
                                                   domain.sfc_kind)
+        if self.order > 0:
+            self.moments = G.multipole_upsweep(ot, self.centers, d["x"], d["y"], d["z"], d["m"], self.order)
+
+    def _far(self):
+        return dict(order=self.order, moments=self.moments) if self.order > 0 else {}
 
     def prepare(self, d, domain, scratch_key: str = "", m2p_out=None):
         """GPU: the upsweep and the interaction lists of the local tree (positions and masses only: they may run
@@ -49,10 +59,11 @@ class MultipoleHolder:
                 # the evaluation buffers and the particles' extent (min_max into gl.mm) are enqueued here, before
                 # lists_done: the P2P phase on the second side stream quantizes its source records with gl.mm and
                 # waits only on lists_done (advisor r5: reading gl.mm unordered after the min_max raced)
-                G._eval_buffers(gl, d["x"], d["y"], d["z"])
+                G._eval_buffers(gl, d["x"], d["y"], d["z"], self.order)
                 self.lists_done = torch.cuda.Event()
                 self.lists_done.record()
-                G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, *m2p_out, phase=1)
+                G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, *m2p_out, phase=1,
+                               **self._far())
                 gl.m2p_done = True
 
     def traverse(self, d, domain, out=None, scratch_key: str = "", prepared: bool = False, m2p_event=None):
@@ -68,16 +79,19 @@ class MultipoleHolder:
             self.last_lists = gl
             if gl is not None and getattr(gl, "m2p_done", False):
                 # M2P ran in prepare (possibly on another stream: m2p_event); P2P here, then the combine after both
-                G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az, phase=2)
+                G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az, phase=2,
+                               **self._far())
                 if m2p_event is not None:
                     torch.cuda.current_stream(d.device).wait_event(m2p_event)
-                parts = [G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az, phase=3)]
+                parts = [G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az, phase=3,
+                                        **self._far())]
             else:
-                parts = [G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az)] if gl else [0.0]
+                parts = [G.gravity_eval(gl, d["x"], d["y"], d["z"], d["h"], d["m"], d.g, ax, ay, az,
+                                        **self._far())] if gl else [0.0]
         else:
             parts = [G.compute_gravity(ot, self.centers, self.multipoles, first, last, d["x"], d["y"], d["z"],
                                        d["h"], d["m"], d.g, ax, ay, az, stats=self.stats, defer=True,
-                                       scratch_key=scratch_key)]
+                                       scratch_key=scratch_key, **self._far())]
         self._rstats = None
         if domain.size > 1 and getattr(domain, "remote_tree", None) is not None:
             rt, rc, rmp = domain.remote_tree

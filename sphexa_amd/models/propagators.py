@@ -65,6 +65,9 @@ class Propagator:
     # sum (MultipoleHolder.traverse_ewald, any number of ranks) on the plain path of _gravity: no side streams, no
     # deferred energy
     ewald_shells = 0
+    # far-field expansion order of the self-gravity (MultipoleHolder): 0 = quadrupoles, P in 1..6 = order-P
+    # Cartesian multipoles over the same interaction lists (GPU, one rank; app/simulation.py check_multipole_order)
+    multipole_order = 0
 
     def __init__(self, out=sys.stdout, rank: int = 0, quiet: bool = False):
         self.out = out if rank == 0 and not quiet else None
@@ -149,7 +152,7 @@ class Propagator:
         if self.gravity is None:
             from .gravity import MultipoleHolder
 
-            self.gravity = MultipoleHolder()
+            self.gravity = MultipoleHolder(self.multipole_order)
         side = getattr(self, "_side_stream", None)
         if side is None:
             side = self._side_stream = torch.cuda.Stream(d.device, priority=GRAVITY_STREAM_PRIORITY)
@@ -185,7 +188,7 @@ class Propagator:
         if self.gravity is None:
             from .gravity import MultipoleHolder
 
-            self.gravity = MultipoleHolder()
+            self.gravity = MultipoleHolder(self.multipole_order)
         main = torch.cuda.current_stream(d.device)
         side = getattr(self, "_side_stream", None)
         if side is None:
@@ -247,7 +250,7 @@ class Propagator:
             if self.gravity is None:
                 from .gravity import MultipoleHolder
 
-                self.gravity = MultipoleHolder()
+                self.gravity = MultipoleHolder(self.multipole_order)
             self.gravity.upsweep(d, domain)
             self.timer.step("Upsweep")
             if self.ewald_shells > 0:

@@ -148,24 +148,39 @@ def gravity_lists(tree: Octree, centers, mp, first: int, last: int, x, y, z, sta
     return gl
 
 
-def _eval_buffers(gl: GravityLists, x, y, z):
-    """P2P partials, the record buffer (16 B per source particle + 40 B per node, gravity.hip
-    gravityRecordsKernel/gravityNodeRecordsKernel) and the particles' extent of an evaluation (kept on ``gl``)"""
-    if getattr(gl, "rec", None) is None:
+def _eval_buffers(gl: GravityLists, x, y, z, order: int = 0):
+    """P2P partials, the record buffer (16 B per source particle + the node record of the expansion order: 40 B for
+    quadrupoles, gravity.hip gravityRecordsKernel/gravityNodeRecordsKernel, else gravity_order.hip) and the
+    particles' extent of an evaluation (kept on ``gl``)"""
+    if getattr(gl, "rec", None) is None or getattr(gl, "rec_order", 0) != order:
         from .reduce import min_max
 
         n, nsrc = gl.last - gl.first, x.numel()
         gl.pacc = torch.empty(4 * n, dtype=torch.float32, device=x.device)  # P2P partials (phi, a) per target
         gl.mm = min_max([x, y, z])
-        gl.rec = torch.empty(4 * nsrc + 10 * gl.tree.num_nodes, dtype=torch.int32, device=x.device)
+        words = _lib.hip().gravity_node_record_bytes(order) // 4
+        gl.rec = torch.empty(4 * nsrc + words * gl.tree.num_nodes, dtype=torch.int32, device=x.device)
+        gl.rec_order = order
     return gl.pacc, gl.rec, gl.mm
 
 
-def gravity_eval(gl: GravityLists, x, y, z, h, m, G: float, ax, ay, az, ugrav=None, phase: int = 0):
+def _check_order(order: int, moments, num_nodes: int):
+    if order == 0:
+        return
+    if not 1 <= order <= 6:
+        raise ValueError("GPU multipole order must be in [1, 6]")
+    if moments is None or moments.dtype != torch.float32 or moments.numel() < multipole_size(order) * num_nodes:
+        raise ValueError("gravity_eval: order-P evaluation needs the float32 moments of multipole_upsweep")
+
+
+def gravity_eval(gl: GravityLists, x, y, z, h, m, G: float, ax, ay, az, ugrav=None, phase: int = 0, order: int = 0,
+                 moments=None):
     """GPU phase 2 of compute_gravity on the lists of ``gl``: M2P + P2P, G a added to ax, ay, az. Returns the
     GravityPending of the evaluation. ``phase`` splits it (gravity.hip computeGravityEval): 1 = M2P (needs no
     smoothing lengths), 2 = P2P, 3 = P2P combine + spilled groups; the caller orders 1 and 2 before 3 and collects
-    the pending values after 3 (the earlier phases return None)"""
+    the pending values after 3 (the earlier phases return None). ``order`` P > 0: the far field of the same lists is
+    the order-P expansion of ``moments`` (multipole_upsweep) instead of the quadrupoles (gravity_order.hip); every
+    phase of one evaluation is given the same order and moments"""
     hp = _lib.hip()
     first, last, tree = gl.first, gl.last, gl.tree
     n = last - first
@@ -173,28 +188,34 @@ def gravity_eval(gl: GravityLists, x, y, z, h, m, G: float, ax, ay, az, ugrav=No
     zb = gl.zb
     st_dev, out = zb[:GravityPending.NSTATS], zb[GravityPending.NSTATS:].view(torch.float64)
     # the P2P kernel generates its source indices from the opened-leaf lists: no index list, no host wait
-    pacc, rec, mm = _eval_buffers(gl, x, y, z)
+    _check_order(order, moments, tree.num_nodes)
+    pacc, rec, mm = _eval_buffers(gl, x, y, z, order)
     hp.gravity_eval(first, last, *gl.tree_args(), x.data_ptr(), y.data_ptr(), z.data_ptr(), h.data_ptr(),
                     m.data_ptr(), float(G), ax.data_ptr(), ay.data_ptr(), az.data_ptr(),
                     0 if ugrav is None else ugrav.data_ptr(), out.data_ptr(), st_dev.data_ptr(),
                     gl.scratch.data_ptr(), cap_m, cap_l, pacc.data_ptr(), x.numel(), tree.num_nodes, rec.data_ptr(),
-                    mm.data_ptr(), _stream(), phase=phase)
+                    mm.data_ptr(), _stream(), phase=phase, order=order,
+                    moments=0 if order == 0 else moments.data_ptr())
     if phase in (0, 3):
         return GravityPending(zb, (n + 63) // 64, (cap_m, cap_l), gl.stats, x.device)
     return None
 
 
 def compute_gravity(tree: Octree, centers, mp, first: int, last: int, x, y, z, h, m, G: float, ax, ay, az,
-                    ugrav=None, stats: dict | None = None, defer: bool = False, scratch_key: str = ""):
+                    ugrav=None, stats: dict | None = None, defer: bool = False, scratch_key: str = "", order: int = 0,
+                    moments=None):
     """add G * a_grav to ax, ay, az for targets [first, last); returns this rank's 0.5 * sum G m phi.
+    ``order`` P > 0 (GPU): order-P far field from ``moments`` (see gravity_eval).
     On the GPU ``stats`` (if given) receives p2p/m2p (summed over targets) and max_p2p/max_m2p (per target).
     ``defer`` (GPU): return a GravityPending instead of copying the energy and statistics to the host here."""
     if last <= first:
         return 0.0
     if x.is_cuda:
         gl = gravity_lists(tree, centers, mp, first, last, x, y, z, stats, scratch_key)
-        pending = gravity_eval(gl, x, y, z, h, m, G, ax, ay, az, ugrav)
+        pending = gravity_eval(gl, x, y, z, h, m, G, ax, ay, az, ugrav, order=order, moments=moments)
         return pending if defer else pending.finish(pending.dev.cpu().tolist())
+    if order:
+        raise ValueError("compute_gravity: the order-P far field runs on device tensors (CPU: compute_gravity_multipole)")
     st = torch.zeros(2, dtype=torch.int64)
     e = float(_lib.cpu().compute_gravity(first, last, tree.child_offsets.data_ptr(), tree.node_to_leaf.data_ptr(),
                                          tree.node_start.data_ptr(), tree.node_end.data_ptr(), centers.data_ptr(),
@@ -621,18 +642,18 @@ def multipole_upsweep(tree: Octree, centers, x, y, z, m, order: int):
 
 def compute_gravity_multipole(tree: Octree, centers, Q, order: int, first: int, last: int, x, y, z, h, m, G: float,
                               ax, ay, az, ugrav=None) -> float:
-    """Barnes-Hut with order-P far field (same MAC and near field as ``compute_gravity``); returns 0.5 sum G m phi"""
+    """Barnes-Hut with order-P far field (same MAC and near field as ``compute_gravity``); returns 0.5 sum G m phi.
+    Device tensors: the interaction lists of ``compute_gravity`` (they depend on the MAC only; the list kernel reads
+    the node masses from quadrupole records, built here) and the order-P evaluation of gravity_order.hip"""
     if last <= first:
         return 0.0
+    if x.is_cuda:
+        # mass-only quadrupole records: the list kernel tests c[3] (the MAC radius) and never the moments
+        mp = zero_(torch.empty(8 * tree.num_nodes, dtype=torch.float32, device=x.device))
+        return compute_gravity(tree, centers, mp, first, last, x, y, z, h, m, G, ax, ay, az, ugrav, order=order,
+                               moments=Q)
     args = (tree.child_offsets.data_ptr(), tree.node_to_leaf.data_ptr(), tree.node_start.data_ptr(),
             tree.node_end.data_ptr(), centers.data_ptr(), Q.data_ptr(), x.data_ptr(), y.data_ptr(), z.data_ptr(),
             h.data_ptr(), m.data_ptr(), float(G), ax.data_ptr(), ay.data_ptr(), az.data_ptr(),
             0 if ugrav is None else ugrav.data_ptr())
-    if x.is_cuda:
-        out = torch.zeros(1, dtype=torch.float64, device=x.device)
-        ovf = torch.zeros(1, dtype=torch.int32, device=x.device)
-        _lib.hip().compute_gravity_multipole(order, first, last, *args, out.data_ptr(), ovf.data_ptr(), _stream())
-        if int(ovf.item()) != 0:
-            raise RuntimeError("multipole traversal stack overflow")
-        return float(out.item())
     return _lib.cpu().compute_gravity_multipole(order, first, last, *args)
