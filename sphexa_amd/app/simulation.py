@@ -120,6 +120,43 @@ class Simulation:
         return dict(etot=d.etot, ecin=d.ecin, eint=d.eint, egrav=d.egrav, linmom=d.linmom, angmom=d.angmom,
                     nsum=d.totalNeighbors)
 
+    def image(self, field: str, kind: str = "slice", axis: str = "z", res=(512, 512), window=None, s0=None, s1=None,
+              weighted: str | None = "default", h_floor: float = 0.5) -> torch.Tensor:
+        """(nv, nu) float32 image of a particle field over all ranks (ops/image.py): a kernel-weighted slice at ``s0``
+        or a column projection over [s0, s1]. ``"rho"`` is the SPH density sum_j m_j W (slice) or the column density
+        sum_j m_j F (projection). Other fields are ``weighted`` by "volume" (sum V A W / sum V W, the default of a
+        slice), by "mass" (sum m A F / sum m F, the default of a projection) or not at all (None: sum V A W, the
+        unnormalised interpolant); pixels that no particle reaches are 0."""
+        from ..ops.image import sph_image
+
+        d, first, last = self.d, self.domain.start_index(), self.domain.end_index()
+        m = d["m"]
+        if weighted == "default":
+            weighted = None if field == "rho" else ("volume" if kind == "slice" else "mass")
+        if weighted not in (None, "volume", "mass"):
+            raise ValueError(f"image: unknown weighting {weighted!r}")
+        if field == "rho":
+            if weighted is not None:
+                raise ValueError("image: rho is the kernel sum of the masses, it takes no weighting")
+            w = [m]
+        else:
+            if weighted == "mass":
+                vol = m
+            elif d.is_allocated("xm") and d.is_allocated("kx"):
+                vol = d["xm"] / d["kx"]
+            elif d.is_allocated("rho"):
+                vol = m / d["rho"]
+            else:
+                raise ValueError("image: a volume weighting needs xm and kx (VE) or rho")
+            w = [vol * d[field].to(torch.float32)] + ([vol] if weighted else [])
+        img = sph_image(d["x"], d["y"], d["z"], d["h"], torch.stack(w).to(torch.float32), self.domain.box, kind=kind,
+                        axis=axis, window=window, res=res, s0=s0, s1=s1, h_floor=h_floor, first=first, last=last,
+                        sinc_index=d.sincIndex)
+        img = self.comm.allreduce(img)
+        if len(w) == 1:
+            return img[0]
+        return torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))
+
     def local(self, name):
         """field values of the locally owned particles"""
         return self.d[name][self.domain.start_index():self.domain.end_index()]

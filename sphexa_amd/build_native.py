@@ -114,7 +114,8 @@ def build_cpu(verbose=False, sanitize=False):
 
 # per-source flags of the HIP module. gravity_order.hip: no packed fp32 VALU instructions (its pair arithmetic is
 # written on scalars; the compiler's own v_pk_*_f32 pairing of independent chains costs operand moves, as above)
-HIP_SOURCE_FLAGS = {"gravity_order.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_SOURCE_FLAGS = {"gravity_order.hip": _NO_PK_F32, "image.hip": _NO_PK_F32}
 
 
 def build_hip(verbose=False, variant=None, defines=()):

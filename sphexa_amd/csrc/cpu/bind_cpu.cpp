@@ -138,6 +138,15 @@ PYBIND11_MODULE(_sphx_cpu, m)
 
     m.def("num_threads", []() { return omp_get_max_threads(); });
 
+    m.def("sph_image",
+          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, const BoxArr& box,
+             const std::array<double, 11>& view, int nu, int nv, Ptr table, int tableLen, Ptr out)
+          {
+              cpu::sphImage(first, last, n, P<double>(x), P<double>(y), P<double>(z), P<float>(h), P<float>(w), C,
+                            makeImageView(toBox(box), view.data(), nu, nv), P<double>(table), tableLen,
+                            P<double>(out));
+          });
+
     m.def("compute_keys", [](int64_t n, Ptr x, Ptr y, Ptr z, const BoxArr& box, int kind, Ptr keys)
           { cpu::computeKeys(n, P<double>(x), P<double>(y), P<double>(z), toBox(box), kind, P<KeyT>(keys)); });
 

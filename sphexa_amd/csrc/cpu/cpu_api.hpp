@@ -107,3 +107,16 @@ void computeStirring(int64_t first, int64_t last, const double* x, const double*
                      const double* phaseIm, const double* amplitudes, double norm);
 
 } // namespace sphx::cpu
+
+#include "sphx/image.hpp"
+
+namespace sphx::cpu
+{
+
+//! SPH slice / column projection of the particles [first, last) (ops/image.py): w = C x n weights, table = F_n in
+//! u = q^2/4, out = C x nv x nu in fp64
+void sphImage(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
+              const float* h, const float* w, int C, const ImageView& V, const double* table, int tableLen,
+              double* out);
+
+} // namespace sphx::cpu

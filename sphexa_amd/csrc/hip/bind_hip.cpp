@@ -633,7 +633,36 @@ PYBIND11_MODULE(_sphx_hip, m)
           "int32-word offsets of the interaction-list slabs in the gravity scratch, the entry tag constants and the\n"
           "capacity of the list kernel's traversal stack");
     m.def("device_checks_enabled", &deviceChecksEnabled);
-    m.def("device_check_flags", []() { return dcheckHydro() | dcheckSfc() | dcheckGravity(); },
+    // ------------------------------------------------------------------------------------------------- images
+    using ViewArr = std::array<double, 11>;
+    m.def("image_records",
+          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, const BoxArr& box,
+             const ViewArr& view, int nu, int nv, Ptr rec, Ptr counts, Ptr s)
+          {
+              imageRecords(first, last, n, P<double>(x), P<double>(y), P<double>(z), P<float>(h), P<float>(w), C,
+                           makeImageView(toBox(box), view.data(), nu, nv), P<ImageRec>(rec), P<int64_t>(counts), St(s));
+          });
+    m.def("image_fill",
+          [](int64_t np, const BoxArr& box, const ViewArr& view, int nu, int nv, Ptr rec, Ptr offsets, Ptr keys, Ptr s)
+          {
+              imageFill(np, makeImageView(toBox(box), view.data(), nu, nv), P<ImageRec>(rec), P<int64_t>(offsets),
+                        P<uint64_t>(keys), St(s));
+          });
+    m.def("image_ranges", [](int64_t total, Ptr keys, int ntiles, int64_t segment, Ptr start, Ptr nseg, Ptr s)
+          { imageRanges(total, P<uint64_t>(keys), ntiles, segment, P<int64_t>(start), P<int64_t>(nseg), St(s)); });
+    m.def("image_tiles",
+          [](int proj, int C, int64_t np, int64_t total, Ptr keys, Ptr rec, const BoxArr& box, const ViewArr& view,
+             int nu, int nv, int ntiles, int64_t segment, int64_t nblocks, Ptr start, Ptr segOff, Ptr table,
+             int tableLen, Ptr work, Ptr img, Ptr s)
+          {
+              const ImageView V = makeImageView(toBox(box), view.data(), nu, nv);
+              if (proj != V.proj) throw std::invalid_argument("image_tiles: kind");
+              imageTiles(C, np, total, P<uint64_t>(keys), P<ImageRec>(rec), V, ntiles, segment, nblocks,
+                         P<int64_t>(start), P<int64_t>(segOff), P<float>(table), tableLen, P<float>(work),
+                         P<float>(img), St(s));
+          });
+
+    m.def("device_check_flags", []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");
     m.def("direct_sum",
           [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr mm, double G, Ptr ax, Ptr ay,

@@ -10,6 +10,7 @@
 
 #include "sphx/box.hpp"
 #include "sphx/cooling.hpp"
+#include "sphx/image.hpp"
 #include "sphx/sph_math.hpp"
 
 namespace sphx::hip
@@ -333,6 +334,20 @@ std::vector<int64_t> gravityScratchLayout(int64_t n, int capM, int capL);
 unsigned dcheckHydro();
 unsigned dcheckSfc();
 unsigned dcheckGravity();
+unsigned dcheckImage();
+
+// image.hip: SPH slices and column projections (ops/image.py holds the sequence: records + counts, scan, fill, sort,
+// ranges, scan, tiles)
+void imageRecords(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
+                  const float* h, const float* w, int C, const ImageView& V, ImageRec* rec, int64_t* counts,
+                  hipStream_t s);
+void imageFill(int64_t np, const ImageView& V, const ImageRec* rec, const int64_t* offsets, uint64_t* keys,
+               hipStream_t s);
+void imageRanges(int64_t total, const uint64_t* keys, int ntiles, int64_t segment, int64_t* start, int64_t* nseg,
+                 hipStream_t s);
+void imageTiles(int C, int64_t np, int64_t total, const uint64_t* keys, const ImageRec* rec, const ImageView& V,
+                int ntiles, int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff,
+                const float* table, int tableLen, float* work, float* img, hipStream_t s);
 bool deviceChecksEnabled();
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,

@@ -14,6 +14,8 @@ Commands:
   set-parms FILE [-a] --key value ...         write settings as file attributes
   radial-profile FILE FIELD [-s STEP] [--bins B]
   slice FILE FIELD [-s STEP] [--axis z] [--width W]
+  image FILE FIELD [-s STEP] [--kind slice|projection] [--axis z] [--res 512] [--device cuda] [-o out.npy]
+                                              SPH-interpolated slice / column projection (ops/image.py)
   substep-timings PROFILE
 """
 
@@ -203,6 +205,44 @@ def cmd_slice(args):
     del ax
 
 
+def cmd_image(args):
+    """kernel-weighted slice (volume-weighted field average, V = m / rho) or mass-weighted column projection of FIELD;
+    ``rho``: the SPH density (slice) or the column density (projection). Writes the (res, res) array as .npy"""
+    import torch
+
+    from ..ops.image import sph_image
+    from ..utils.box import Box
+
+    io = _lib.io()
+    f = io.open(args.file, "r")
+    g = io.open_step(f, io.num_steps(f) - 1 if args.step is None else
+                     next((s for s, it, _ in _steps(args.file) if it == args.step), io.num_steps(f) - 1))
+    attrs = dict(io.read_attrs(g))
+    io.close_group(g)
+    io.close(f)
+    box = Box.from_attributes(np.ravel(attrs["box"]), np.ravel(attrs["boundaryType"]))
+    need = ["x", "y", "z", "h", "m"] + ([] if args.field == "rho" else
+                                        (["vx", "vy", "vz"] if args.field == "v" else [args.field]))
+    need += ["rho"] if args.field != "rho" and args.kind == "slice" else []
+    d = _read(args.file, args.step, need)
+    dev = torch.device(args.device)
+    m = d["m"]
+    if args.field == "rho":
+        w = [m]
+    else:
+        vol = m / d["rho"] if args.kind == "slice" else m
+        w = [vol * _quantity(d, args.field), vol]
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
+    img = sph_image(t(d["x"], torch.float64), t(d["y"], torch.float64), t(d["z"], torch.float64),
+                    t(d["h"], torch.float32), t(np.stack(w), torch.float32), box, kind=args.kind, axis=args.axis,
+                    res=(args.res, args.res), sinc_index=float(np.ravel(attrs.get("sincIndex", [6.0]))[0]))
+    img = (img[0] if len(w) == 1 else torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))).cpu().numpy()
+    out = args.out or f"image_{args.field}.npy"
+    np.save(out, img)
+    print(f"wrote {out}: {args.kind} of {args.field} along {args.axis}, {img.shape[1]} x {img.shape[0]} pixels, "
+          f"min {img.min():.6e} max {img.max():.6e}")
+
+
 def cmd_substep_timings(args):
     """the profile file holds blocks: 'numRanks R numIterations K', a header of substep names, one row of times"""
     with open(args.profile) as fh:
@@ -252,6 +292,15 @@ def main(argv=None):
             p.add_argument("--axis", default="z")
             p.add_argument("--center", type=float, default=0.0)
             p.add_argument("--width", type=float, default=0.02)
+    p = sub.add_parser("image")
+    p.add_argument("file")
+    p.add_argument("field")
+    p.add_argument("-s", "--step", type=int, default=None)
+    p.add_argument("--kind", choices=["slice", "projection"], default="slice")
+    p.add_argument("--axis", default="z", choices=["x", "y", "z"])
+    p.add_argument("--res", type=int, default=512)
+    p.add_argument("--device", default="cuda")
+    p.add_argument("-o", "--out", default=None)
     p = sub.add_parser("substep-timings")
     p.add_argument("profile")
     args, extra = ap.parse_known_args(argv)
@@ -261,7 +310,7 @@ def main(argv=None):
         if extra:
             ap.error(f"unrecognized arguments: {' '.join(extra)}")
         {"steps": cmd_steps, "add-m1": cmd_add_m1, "init-file": cmd_init_file, "radial-profile": cmd_radial_profile,
-         "slice": cmd_slice, "substep-timings": cmd_substep_timings}[args.cmd](args)
+         "slice": cmd_slice, "image": cmd_image, "substep-timings": cmd_substep_timings}[args.cmd](args)
     return 0
 
 
