@@ -130,25 +130,7 @@ class Simulation:
         from ..ops.image import sph_image
 
         d, first, last = self.d, self.domain.start_index(), self.domain.end_index()
-        m = d["m"]
-        if weighted == "default":
-            weighted = None if field == "rho" else ("volume" if kind == "slice" else "mass")
-        if weighted not in (None, "volume", "mass"):
-            raise ValueError(f"image: unknown weighting {weighted!r}")
-        if field == "rho":
-            if weighted is not None:
-                raise ValueError("image: rho is the kernel sum of the masses, it takes no weighting")
-            w = [m]
-        else:
-            if weighted == "mass":
-                vol = m
-            elif d.is_allocated("xm") and d.is_allocated("kx"):
-                vol = d["xm"] / d["kx"]
-            elif d.is_allocated("rho"):
-                vol = m / d["rho"]
-            else:
-                raise ValueError("image: a volume weighting needs xm and kx (VE) or rho")
-            w = [vol * d[field].to(torch.float32)] + ([vol] if weighted else [])
+        w = self._field_weights("image", [field], weighted, "volume" if kind == "slice" else "mass")
         img = sph_image(d["x"], d["y"], d["z"], d["h"], torch.stack(w).to(torch.float32), self.domain.box, kind=kind,
                         axis=axis, window=window, res=res, s0=s0, s1=s1, h_floor=h_floor, first=first, last=last,
                         sinc_index=d.sincIndex)
@@ -156,6 +138,75 @@ class Simulation:
         if len(w) == 1:
             return img[0]
         return torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))
+
+    def _field_weights(self, what, fields, weighted, default):
+        """per-particle channel weights of image, volume and power_spectrum: [m] for ``rho`` (the kernel sum of the
+        masses), else vol * field for every field and, if ``weighted``, the normaliser vol last; vol = m ("mass") or
+        the particle volume (xm / kx of VE, else m / rho)"""
+        d, m = self.d, self.d["m"]
+        if weighted == "default":
+            weighted = None if fields == ["rho"] else default
+        if weighted not in (None, "volume", "mass"):
+            raise ValueError(f"{what}: unknown weighting {weighted!r}")
+        if fields == ["rho"]:
+            if weighted is not None:
+                raise ValueError(f"{what}: rho is the kernel sum of the masses, it takes no weighting")
+            return [m]
+        if weighted == "mass":
+            vol = m
+        elif d.is_allocated("xm") and d.is_allocated("kx"):
+            vol = d["xm"] / d["kx"]
+        elif d.is_allocated("rho"):
+            vol = m / d["rho"]
+        else:
+            raise ValueError(f"{what}: a volume weighting needs xm and kx (VE) or rho")
+        return [vol * d[f].to(torch.float32) for f in fields] + ([vol] if weighted else [])
+
+    def _volume_channels(self, w, res, window, h_floor):
+        """the channels ``w`` on the grid (ops/volume.py), summed over the ranks"""
+        from ..ops.volume import sph_volume
+
+        d = self.d
+        vol = sph_volume(d["x"], d["y"], d["z"], d["h"], torch.stack(w).to(torch.float32), self.domain.box, res=res,
+                         window=window, h_floor=h_floor, first=self.domain.start_index(),
+                         last=self.domain.end_index(), sinc_index=d.sincIndex)
+        return self.comm.allreduce(vol)
+
+    def volume(self, field: str, res=(128, 128, 128), window=None, weighted: str | None = "default",
+               h_floor: float = 0.5) -> torch.Tensor:
+        """(nz, ny, nx) float32 grid of a particle field over all ranks (ops/volume.py), ``res`` = (nx, ny, nz),
+        ``window`` = (lo3, hi3) (default: the box). The weightings are those of ``image``: ``"rho"`` is the SPH density
+        sum_j m_j W, other fields are ``weighted`` by "volume" (the default), by "mass" or not at all (None)"""
+        w = self._field_weights("volume", [field], weighted, "volume")
+        vol = self._volume_channels(w, res, window, h_floor)
+        if len(w) == 1:
+            return vol[0]
+        return torch.where(vol[1] != 0, vol[0] / vol[1], torch.zeros_like(vol[0]))
+
+    def power_spectrum(self, fields=("vx", "vy", "vz"), res: int = 128, weighted: str = "volume", window=None):
+        """(k, P, count) of ops/spectrum.py for up to three fields interpolated onto a res^3 grid: one sph_volume call
+        carries the weighted components and the normaliser, the ratios are formed after the reduction over the ranks.
+        Needs a cubic, fully periodic box or an explicit cubic ``window`` = (lo3, hi3)"""
+        from ..ops.spectrum import power_spectrum
+        from ..utils.box import PERIODIC
+
+        box, fields = self.domain.box, list(fields)
+        if window is None:
+            if any(b != PERIODIC for b in box.bc):
+                raise ValueError("power_spectrum: the box is not fully periodic; give a cubic window")
+            window = (box.lo, box.hi)
+        edges = [float(b) - float(a) for a, b in zip(*window)]
+        if len(edges) != 3 or not all(abs(e - edges[0]) <= 1e-12 * abs(edges[0]) for e in edges):
+            raise ValueError(f"power_spectrum: the window is not cubic (edges {edges})")
+        if not 1 <= len(fields) <= 3 or weighted not in ("volume", "mass"):
+            raise ValueError("power_spectrum: one to three fields, weighted by volume or mass")
+        w = self._field_weights("power_spectrum", fields, weighted, weighted)
+        n = len(fields)
+        if n == 2:  # (channel counts are 1, 2 or 4: the components, a zero channel, the normaliser last)
+            w.insert(2, torch.zeros_like(w[-1]))
+        grid = self._volume_channels(w, (int(res),) * 3, window, 0.5)
+        u = torch.where(grid[-1:] != 0, grid[:n] / grid[-1:], torch.zeros_like(grid[:n]))
+        return power_spectrum(u.contiguous())
 
     def local(self, name):
         """field values of the locally owned particles"""

@@ -147,6 +147,14 @@ PYBIND11_MODULE(_sphx_cpu, m)
                             P<double>(out));
           });
 
+    m.def("sph_volume",
+          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, const BoxArr& box,
+             const std::array<double, 9>& view, const std::array<int, 3>& res, Ptr out)
+          {
+              cpu::sphVolume(first, last, n, P<double>(x), P<double>(y), P<double>(z), P<float>(h), P<float>(w), C,
+                             makeVolumeView(toBox(box), view.data(), res[0], res[1], res[2]), P<double>(out));
+          });
+
     m.def("compute_keys", [](int64_t n, Ptr x, Ptr y, Ptr z, const BoxArr& box, int kind, Ptr keys)
           { cpu::computeKeys(n, P<double>(x), P<double>(y), P<double>(z), toBox(box), kind, P<KeyT>(keys)); });
 

@@ -120,3 +120,14 @@ void sphImage(int64_t first, int64_t last, int64_t n, const double* x, const dou
               double* out);
 
 } // namespace sphx::cpu
+
+#include "sphx/volume.hpp"
+
+namespace sphx::cpu
+{
+
+//! SPH volume of the particles [first, last) (ops/volume.py): w = C x n weights, out = C x nz x ny x nx in fp64
+void sphVolume(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
+               const float* h, const float* w, int C, const VolumeView& V, double* out);
+
+} // namespace sphx::cpu

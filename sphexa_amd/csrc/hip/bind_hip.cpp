@@ -662,7 +662,45 @@ PYBIND11_MODULE(_sphx_hip, m)
                          P<float>(img), St(s));
           });
 
-    m.def("device_check_flags", []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage(); },
+    // ------------------------------------------------------------------------------------------------ volumes
+    using VolArr = std::array<double, 9>;
+    using Res3   = std::array<int, 3>;
+    m.def("volume_records",
+          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, const BoxArr& box,
+             const VolArr& view, const Res3& res, Ptr rec, Ptr counts, Ptr s)
+          {
+              volumeRecords(first, last, n, P<double>(x), P<double>(y), P<double>(z), P<float>(h), P<float>(w), C,
+                            makeVolumeView(toBox(box), view.data(), res[0], res[1], res[2]), P<VolumeRec>(rec),
+                            P<int64_t>(counts), St(s));
+          });
+    m.def("volume_fill",
+          [](int64_t np, const BoxArr& box, const VolArr& view, const Res3& res, Ptr rec, Ptr offsets, Ptr keys, Ptr s)
+          {
+              volumeFill(np, makeVolumeView(toBox(box), view.data(), res[0], res[1], res[2]), P<VolumeRec>(rec),
+                         P<int64_t>(offsets), P<uint64_t>(keys), St(s));
+          });
+    m.def("volume_ranges",
+          [](int64_t total, Ptr keys, int64_t nbricks, int64_t segment, Ptr start, Ptr nseg, Ptr wseg, Ptr s)
+          {
+              volumeRanges(total, P<uint64_t>(keys), nbricks, segment, P<int64_t>(start), P<int64_t>(nseg),
+                           P<int64_t>(wseg), St(s));
+          });
+    m.def("volume_bricks",
+          [](int C, int64_t np, int64_t total, Ptr keys, Ptr rec, const BoxArr& box, const VolArr& view,
+             const Res3& res, int64_t nbricks, int64_t segment, int64_t nblocks, Ptr start, Ptr segOff, Ptr workOff,
+             int64_t nwork, Ptr work, Ptr vol, Ptr s)
+          {
+              volumeBricks(C, np, total, P<uint64_t>(keys), P<VolumeRec>(rec),
+                           makeVolumeView(toBox(box), view.data(), res[0], res[1], res[2]), nbricks, segment, nblocks,
+                           P<int64_t>(start), P<int64_t>(segOff), P<int64_t>(workOff), nwork, P<float>(work),
+                           P<float>(vol), St(s));
+          });
+    m.def("spectrum_shell_blocks", &spectrumShellBlocks);
+    m.def("spectrum_shells", [](int C, int N, Ptr spec, int nbins, Ptr partial, Ptr out, Ptr s)
+          { spectrumShells(C, N, P<float>(spec), nbins, P<double>(partial), P<double>(out), St(s)); });
+
+    m.def("device_check_flags",
+          []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");
     m.def("direct_sum",
           [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr mm, double G, Ptr ax, Ptr ay,

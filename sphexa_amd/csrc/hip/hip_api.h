@@ -12,6 +12,7 @@
 #include "sphx/cooling.hpp"
 #include "sphx/image.hpp"
 #include "sphx/sph_math.hpp"
+#include "sphx/volume.hpp"
 
 namespace sphx::hip
 {
@@ -348,6 +349,24 @@ void imageRanges(int64_t total, const uint64_t* keys, int ntiles, int64_t segmen
 void imageTiles(int C, int64_t np, int64_t total, const uint64_t* keys, const ImageRec* rec, const ImageView& V,
                 int ntiles, int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff,
                 const float* table, int tableLen, float* work, float* img, hipStream_t s);
+
+// volume.hip: SPH volumes on 3-D grids, binned to 8^3-voxel bricks (ops/volume.py holds the sequence: records +
+// counts, scan, fill, sort, ranges, scan, bricks), and the shell binning of a half spectrum (ops/spectrum.py)
+unsigned dcheckVolume();
+void volumeRecords(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
+                   const float* h, const float* w, int C, const VolumeView& V, VolumeRec* rec, int64_t* counts,
+                   hipStream_t s);
+void volumeFill(int64_t np, const VolumeView& V, const VolumeRec* rec, const int64_t* offsets, uint64_t* keys,
+                hipStream_t s);
+void volumeRanges(int64_t total, const uint64_t* keys, int64_t nbricks, int64_t segment, int64_t* start,
+                  int64_t* nseg, int64_t* wseg, hipStream_t s);
+void volumeBricks(int C, int64_t np, int64_t total, const uint64_t* keys, const VolumeRec* rec, const VolumeView& V,
+                  int64_t nbricks, int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff,
+                  const int64_t* workOff, int64_t nwork, float* work, float* vol, hipStream_t s);
+//! blocks (= partial rows of 2 nbins doubles) that spectrumShells writes for a grid of N^3
+int spectrumShellBlocks(int N);
+//! spec: C x N x N x (N/2 + 1) complex64 (rfftn, unnormalised); out: P[nbins] then count[nbins]
+void spectrumShells(int C, int N, const float* spec, int nbins, double* partial, double* out, hipStream_t s);
 bool deviceChecksEnabled();
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,

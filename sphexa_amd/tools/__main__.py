@@ -16,6 +16,10 @@ Commands:
   slice FILE FIELD [-s STEP] [--axis z] [--width W]
   image FILE FIELD [-s STEP] [--kind slice|projection] [--axis z] [--res 512] [--device cuda] [-o out.npy]
                                               SPH-interpolated slice / column projection (ops/image.py)
+  volume FILE FIELD [-s STEP] [--res 128] [--device cuda] [-o out.npy]
+                                              SPH-interpolated (res, res, res) grid of FIELD (ops/volume.py)
+  spectrum FILE [-s STEP] [--fields vx,vy,vz] [--res 128] [--device cuda] [-o spectrum.txt]
+                                              shell-binned power spectrum of the interpolated fields: k, P, count
   substep-timings PROFILE
 """
 
@@ -205,12 +209,8 @@ def cmd_slice(args):
     del ax
 
 
-def cmd_image(args):
-    """kernel-weighted slice (volume-weighted field average, V = m / rho) or mass-weighted column projection of FIELD;
-    ``rho``: the SPH density (slice) or the column density (projection). Writes the (res, res) array as .npy"""
-    import torch
-
-    from ..ops.image import sph_image
+def _step_box(args):
+    """(step attributes, box) of the step that ``args`` names (default: the last)"""
     from ..utils.box import Box
 
     io = _lib.io()
@@ -220,7 +220,17 @@ def cmd_image(args):
     attrs = dict(io.read_attrs(g))
     io.close_group(g)
     io.close(f)
-    box = Box.from_attributes(np.ravel(attrs["box"]), np.ravel(attrs["boundaryType"]))
+    return attrs, Box.from_attributes(np.ravel(attrs["box"]), np.ravel(attrs["boundaryType"]))
+
+
+def cmd_image(args):
+    """kernel-weighted slice (volume-weighted field average, V = m / rho) or mass-weighted column projection of FIELD;
+    ``rho``: the SPH density (slice) or the column density (projection). Writes the (res, res) array as .npy"""
+    import torch
+
+    from ..ops.image import sph_image
+
+    attrs, box = _step_box(args)
     need = ["x", "y", "z", "h", "m"] + ([] if args.field == "rho" else
                                         (["vx", "vy", "vz"] if args.field == "v" else [args.field]))
     need += ["rho"] if args.field != "rho" and args.kind == "slice" else []
@@ -241,6 +251,64 @@ def cmd_image(args):
     np.save(out, img)
     print(f"wrote {out}: {args.kind} of {args.field} along {args.axis}, {img.shape[1]} x {img.shape[0]} pixels, "
           f"min {img.min():.6e} max {img.max():.6e}")
+
+
+def _snapshot_grid(args, fields):
+    """FIELD(s) of a step on a (res, res, res) grid over the box: the volume-weighted averages sum V A W / sum V W,
+    V = m / rho (``rho`` alone: the SPH density sum m W), as a (len(fields), res, res, res) float32 tensor"""
+    import torch
+
+    from ..ops.volume import sph_volume
+
+    attrs, box = _step_box(args)
+    density = fields == ["rho"]
+    if len(fields) > 3 or (not density and "rho" in fields):
+        raise SystemExit("one to three fields; rho only on its own")
+    need = ["x", "y", "z", "h", "m"] + ([] if density else ["rho"])
+    for name in fields:
+        need += [] if name == "rho" else (["vx", "vy", "vz"] if name == "v" else [name])
+    d = _read(args.file, args.step, list(dict.fromkeys(need)))
+    dev = torch.device(args.device)
+    if density:
+        w = [d["m"]]
+    else:
+        vol = d["m"] / d["rho"]
+        w = [vol * _quantity(d, name) for name in fields]
+        w += [np.zeros_like(vol)] * (len(w) == 2) + [vol]  # 2 or 4 channels, the normaliser last
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
+    grid = sph_volume(t(d["x"], torch.float64), t(d["y"], torch.float64), t(d["z"], torch.float64),
+                      t(d["h"], torch.float32), t(np.stack(w), torch.float32), box, res=(args.res,) * 3,
+                      sinc_index=float(np.ravel(attrs.get("sincIndex", [6.0]))[0]))
+    if density:
+        return grid, box
+    n = len(fields)
+    return torch.where(grid[-1:] != 0, grid[:n] / grid[-1:], torch.zeros_like(grid[:n])).contiguous(), box
+
+
+def cmd_volume(args):
+    """kernel-weighted grid of FIELD over the box. Writes the (res, res, res) array, indexed (z, y, x), as .npy"""
+    grid, _ = _snapshot_grid(args, [args.field])
+    vol = grid[0].cpu().numpy()
+    out = args.out or f"volume_{args.field}.npy"
+    np.save(out, vol)
+    print(f"wrote {out}: {args.field} on {vol.shape[2]} x {vol.shape[1]} x {vol.shape[0]} voxels, "
+          f"min {vol.min():.6e} max {vol.max():.6e}")
+
+
+def cmd_spectrum(args):
+    """power spectrum of the interpolated fields (default: the velocity) over a cubic box: text columns k, P, count"""
+    from ..ops.spectrum import power_spectrum
+    from ..utils.box import PERIODIC
+
+    fields = args.fields.split(",")
+    grid, box = _snapshot_grid(args, fields)
+    L = box.lengths()
+    if max(L) - min(L) > 1e-12 * max(L) or any(b != PERIODIC for b in box.bc):
+        raise SystemExit(f"spectrum: the box is not cubic and fully periodic (edges {L}, boundaries {box.bc})")
+    k, P, count = (t.cpu().numpy() for t in power_spectrum(grid))
+    out = args.out or "spectrum.txt"
+    np.savetxt(out, np.stack([k, P, count], axis=1), header=f"k P count  ({','.join(fields)}, {args.res}^3)")
+    print(f"wrote {out}: {len(k)} shells, sum P {P.sum():.6e}")
 
 
 def cmd_substep_timings(args):
@@ -301,6 +369,17 @@ def main(argv=None):
     p.add_argument("--res", type=int, default=512)
     p.add_argument("--device", default="cuda")
     p.add_argument("-o", "--out", default=None)
+    for name in ("volume", "spectrum"):
+        p = sub.add_parser(name)
+        p.add_argument("file")
+        if name == "volume":
+            p.add_argument("field")
+        else:
+            p.add_argument("--fields", default="vx,vy,vz")
+        p.add_argument("-s", "--step", type=int, default=None)
+        p.add_argument("--res", type=int, default=128)
+        p.add_argument("--device", default="cuda")
+        p.add_argument("-o", "--out", default=None)
     p = sub.add_parser("substep-timings")
     p.add_argument("profile")
     args, extra = ap.parse_known_args(argv)
@@ -310,7 +389,8 @@ def main(argv=None):
         if extra:
             ap.error(f"unrecognized arguments: {' '.join(extra)}")
         {"steps": cmd_steps, "add-m1": cmd_add_m1, "init-file": cmd_init_file, "radial-profile": cmd_radial_profile,
-         "slice": cmd_slice, "image": cmd_image, "substep-timings": cmd_substep_timings}[args.cmd](args)
+         "slice": cmd_slice, "image": cmd_image, "volume": cmd_volume, "spectrum": cmd_spectrum,
+         "substep-timings": cmd_substep_timings}[args.cmd](args)
     return 0
 
 
