@@ -208,6 +208,32 @@ class Simulation:
         u = torch.where(grid[-1:] != 0, grid[:n] / grid[-1:], torch.zeros_like(grid[:n]))
         return power_spectrum(u.contiguous())
 
+    def find_groups(self, b: float = 0.2, linking_length: float | None = None, rho_min: float | None = None,
+                    min_members: int = 20):
+        """friends-of-friends groups of the owned particles (ops/fof.py): (labels, catalogue). The linking length
+        defaults to ``b`` mean particle spacings, b (V_box / N_total)^(1/3); ``rho_min`` lets only the particles with
+        rho >= rho_min take part. One rank only: groups are not merged across ranks"""
+        from ..ops.fof import fof_catalog, fof_labels
+
+        if self.comm.size > 1:
+            raise NotImplementedError("find_groups: groups are not merged across ranks yet; run on one rank or "
+                                      "call it on a gathered snapshot (python -m sphexa_amd.tools fof)")
+        d, box = self.d, self.domain.box
+        first, last = self.domain.start_index(), self.domain.end_index()
+        if linking_length is None:
+            lx, ly, lz = box.lengths()
+            linking_length = b * (lx * ly * lz / float(d.numParticlesGlobal)) ** (1.0 / 3.0)
+        select = None
+        if rho_min is not None:
+            if not d.is_allocated("rho"):
+                raise ValueError("find_groups: rho_min needs the density field rho, which this run does not hold")
+            select = d["rho"] >= float(rho_min)
+        labels = fof_labels(d["x"], d["y"], d["z"], box, linking_length, select=select, first=first, last=last)
+        own = lambda name: d[name][first:last]
+        cat = fof_catalog(labels, own("x"), own("y"), own("z"), own("m"), box, min_members=min_members,
+                          v=(own("vx"), own("vy"), own("vz")))
+        return labels, cat
+
     def local(self, name):
         """field values of the locally owned particles"""
         return self.d[name][self.domain.start_index():self.domain.end_index()]

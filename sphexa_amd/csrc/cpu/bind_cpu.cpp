@@ -155,6 +155,22 @@ PYBIND11_MODULE(_sphx_cpu, m)
                              makeVolumeView(toBox(box), view.data(), res[0], res[1], res[2]), P<double>(out));
           });
 
+    m.def("fof_labels",
+          [](int64_t np, Ptr x, Ptr y, Ptr z, Ptr select, const BoxArr& box, double b, const std::array<double, 6>& ext,
+             Ptr label)
+          {
+              cpu::fofLabels(np, P<double>(x), P<double>(y), P<double>(z), P<uint8_t>(select), toBox(box),
+                             makeFofGrid(toBox(box), b, ext.data()), P<int32_t>(label));
+          });
+    m.def("fof_catalog",
+          [](int64_t n, Ptr label, Ptr x, Ptr y, Ptr z, Ptr mm, Ptr vx, Ptr vy, Ptr vz, const BoxArr& box,
+             int64_t minMembers)
+          {
+              auto c = cpu::fofCatalog(n, P<int32_t>(label), P<double>(x), P<double>(y), P<double>(z), P<double>(mm),
+                                       P<double>(vx), P<double>(vy), P<double>(vz), toBox(box), minMembers);
+              return py::make_tuple(toNumpy(c.label), toNumpy(c.count), toNumpy(c.sums));
+          });
+
     m.def("compute_keys", [](int64_t n, Ptr x, Ptr y, Ptr z, const BoxArr& box, int kind, Ptr keys)
           { cpu::computeKeys(n, P<double>(x), P<double>(y), P<double>(z), toBox(box), kind, P<KeyT>(keys)); });
 

@@ -131,3 +131,27 @@ void sphVolume(int64_t first, int64_t last, int64_t n, const double* x, const do
                const float* h, const float* w, int C, const VolumeView& V, double* out);
 
 } // namespace sphx::cpu
+
+#include "sphx/fof.hpp"
+
+namespace sphx::cpu
+{
+
+//! friends-of-friends labels of np particles (ops/fof.py): select may be null; label[i] = smallest particle of i's
+//! group, -1 for particles that take no part
+void fofLabels(int64_t np, const double* x, const double* y, const double* z, const uint8_t* select, const Box& box,
+               const FofGrid& g, int32_t* label);
+
+//! groups of at least minMembers, count descending then label ascending; sums: 7 doubles per group
+//! {mass, com x, y, z, vel x, y, z}
+struct FofCatalog
+{
+    std::vector<int32_t> label;
+    std::vector<int64_t> count;
+    std::vector<double> sums;
+};
+FofCatalog fofCatalog(int64_t n, const int32_t* label, const double* x, const double* y, const double* z,
+                      const double* m, const double* vx, const double* vy, const double* vz, const Box& box,
+                      int64_t minMembers);
+
+} // namespace sphx::cpu

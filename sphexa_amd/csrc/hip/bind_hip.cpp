@@ -662,6 +662,49 @@ PYBIND11_MODULE(_sphx_hip, m)
                          P<float>(img), St(s));
           });
 
+    // ------------------------------------------------------------------------------------- friends-of-friends
+    using Ext6 = std::array<double, 6>;
+    // bufs: the fields of FofBuffers in their order (tmpBytes last, as a number)
+    auto fofBuffers = [](const std::vector<Ptr>& b)
+    {
+        if (b.size() != 16) throw std::invalid_argument("fof: 16 buffer entries");
+        return FofBuffers{P<uint64_t>(b[0]), P<uint64_t>(b[1]), P<int32_t>(b[2]),  P<float4>(b[3]),
+                          P<float4>(b[4]),   P<int64_t>(b[5]),  P<int32_t>(b[6]),  P<int32_t>(b[7]),
+                          P<int64_t>(b[8]),  P<int32_t>(b[9]),  P<int32_t>(b[10]), P<int32_t>(b[11]),
+                          P<int32_t>(b[12]), P<int64_t>(b[13]), P<void>(b[14]),    size_t(b[15])};
+    };
+    m.def("fof_prepare",
+          [fofBuffers](int64_t np, Ptr x, Ptr y, Ptr z, Ptr select, const BoxArr& box, double b, const Ext6& ext,
+                       const std::vector<Ptr>& bufs, Ptr s)
+          {
+              fofPrepare(np, P<double>(x), P<double>(y), P<double>(z), P<uint8_t>(select),
+                         makeFofGrid(toBox(box), b, ext.data()), fofBuffers(bufs), St(s));
+          });
+    m.def("fof_link",
+          [fofBuffers](int64_t np, int64_t ns, int64_t ncells, int64_t nItems, Ptr x, Ptr y, Ptr z, const BoxArr& box,
+                       double b, const Ext6& ext, const std::vector<Ptr>& bufs, Ptr stats, Ptr label, Ptr s)
+          {
+              fofLink(np, ns, ncells, nItems, P<double>(x), P<double>(y), P<double>(z), toBox(box),
+                      makeFofGrid(toBox(box), b, ext.data()), fofBuffers(bufs), P<unsigned long long>(stats),
+                      P<int32_t>(label), St(s));
+          });
+    m.def("fof_groups",
+          [](int64_t n, Ptr label, int64_t minMembers, Ptr keys, Ptr keysSorted, Ptr perm, Ptr scan, Ptr gstart,
+             Ptr counts, Ptr tmp, size_t tmpBytes, Ptr s)
+          {
+              fofGroups(n, P<int32_t>(label), minMembers, P<uint64_t>(keys), P<uint64_t>(keysSorted), P<int32_t>(perm),
+                        P<int64_t>(scan), P<int32_t>(gstart), P<int64_t>(counts), P<void>(tmp), tmpBytes, St(s));
+          });
+    m.def("fof_sums",
+          [](int64_t n, int64_t Gall, int64_t G, Ptr perm2, Ptr gstart, Ptr perm, Ptr keysSorted, Ptr x, Ptr y, Ptr z,
+             Ptr mm, Ptr vx, Ptr vy, Ptr vz, const BoxArr& box, Ptr label, Ptr count, Ptr mass, Ptr com, Ptr vel, Ptr s)
+          {
+              fofSums(n, Gall, G, P<int32_t>(perm2), P<int32_t>(gstart), P<int32_t>(perm), P<uint64_t>(keysSorted),
+                      P<double>(x), P<double>(y), P<double>(z), P<double>(mm), P<double>(vx), P<double>(vy),
+                      P<double>(vz), toBox(box), P<int32_t>(label), P<int64_t>(count), P<double>(mass),
+                      P<double>(com), P<double>(vel), St(s));
+          });
+
     // ------------------------------------------------------------------------------------------------ volumes
     using VolArr = std::array<double, 9>;
     using Res3   = std::array<int, 3>;

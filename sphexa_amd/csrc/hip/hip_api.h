@@ -10,6 +10,7 @@
 
 #include "sphx/box.hpp"
 #include "sphx/cooling.hpp"
+#include "sphx/fof.hpp"
 #include "sphx/image.hpp"
 #include "sphx/sph_math.hpp"
 #include "sphx/volume.hpp"
@@ -368,6 +369,40 @@ int spectrumShellBlocks(int N);
 //! spec: C x N x N x (N/2 + 1) complex64 (rfftn, unnormalised); out: P[nbins] then count[nbins]
 void spectrumShells(int C, int N, const float* spec, int nbins, double* partial, double* out, hipStream_t s);
 bool deviceChecksEnabled();
+
+// fof.hip: friends-of-friends groups (ops/fof.py holds the sequence: prepare, one read of the counts, link; for the
+// catalogue: groups, one read of the counts, a sort of the order keys, sums)
+struct FofBuffers
+{
+    uint64_t *keys, *keysSorted; // np each
+    int32_t* perm;               // np
+    float4 *recIn, *rec;         // np each
+    int64_t* scan;               // np + 1
+    int32_t *cellOf, *cellStart; // np, np + 1
+    int64_t* cellKey;            // np
+    int32_t *parent, *least, *root, *itemStart; // np, np, np, np + 1
+    int64_t* counts;             // 4, zeroed: selected particles, occupied cells, items
+    void* tmp;                   // the larger of the sort's and the scan's workspace for np + 1 elements
+    size_t tmpBytes;
+};
+//! keys, sort, cells, work items: everything before the link kernel; then counts holds the sizes it runs on
+void fofPrepare(int64_t np, const double* x, const double* y, const double* z, const uint8_t* select,
+                const FofGrid& g, const FofBuffers& B, hipStream_t s);
+//! link kernel, flatten, labels; stats (may be null): 4 zeroed counters, see fof.hip FofLinkArgs
+void fofLink(int64_t np, int64_t ns, int64_t ncells, int64_t nItems, const double* x, const double* y, const double* z,
+             const Box& box, const FofGrid& g, const FofBuffers& B, unsigned long long* stats, int32_t* label,
+             hipStream_t s);
+//! labels sorted into groups: counts[0] = groups, counts[1] = groups of at least minMembers, whose order keys
+//! (count descending, label ascending; the others behind them) are left in keys[0 .. groups)
+void fofGroups(int64_t n, const int32_t* label, int64_t minMembers, uint64_t* keys, uint64_t* keysSorted,
+               int32_t* perm, int64_t* scan, int32_t* gstart, int64_t* counts, void* tmp, size_t tmpBytes,
+               hipStream_t s);
+//! the first G groups in the order perm2 of their sorted order keys: label, count, mass, centre of mass, velocity
+//! (vx null: none)
+void fofSums(int64_t n, int64_t Gall, int64_t G, const int32_t* perm2, const int32_t* gstart, const int32_t* perm,
+             const uint64_t* keysSorted, const double* x, const double* y, const double* z, const double* m,
+             const double* vx, const double* vy, const double* vz, const Box& box, int32_t* label, int64_t* count,
+             double* mass, double* com, double* vel, hipStream_t s);
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
                          const double* z, unsigned long long* stats, void* scratch, int testFrontCap, int capM,

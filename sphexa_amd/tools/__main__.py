@@ -20,6 +20,8 @@ Commands:
                                               SPH-interpolated (res, res, res) grid of FIELD (ops/volume.py)
   spectrum FILE [-s STEP] [--fields vx,vy,vz] [--res 128] [--device cuda] [-o spectrum.txt]
                                               shell-binned power spectrum of the interpolated fields: k, P, count
+  fof FILE [-s STEP] [--b 0.2 | --ll L] [--rho-min R] [--min-members 20] [--device cuda] [-o groups.txt]
+      [--labels labels.npy]                   friends-of-friends groups (ops/fof.py): label count mass cx cy cz vx vy vz
   substep-timings PROFILE
 """
 
@@ -311,6 +313,36 @@ def cmd_spectrum(args):
     print(f"wrote {out}: {len(k)} shells, sum P {P.sum():.6e}")
 
 
+def cmd_fof(args):
+    """friends-of-friends group catalogue of a step as text columns; the linking length is ``--ll`` or ``--b`` mean
+    particle spacings of the box"""
+    import torch
+
+    from ..ops.fof import fof_catalog, fof_labels
+
+    _, box = _step_box(args)
+    names = ["x", "y", "z", "m", "vx", "vy", "vz"] + (["rho"] if args.rho_min is not None else [])
+    d = _read(args.file, args.step, names)
+    dev = torch.device(args.device)
+    t = {k: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev) for k, a in d.items()}
+    n = t["x"].numel()
+    lx, ly, lz = box.lengths()
+    ll = args.ll if args.ll is not None else args.b * (lx * ly * lz / n) ** (1.0 / 3.0)
+    select = None if args.rho_min is None else t["rho"] >= args.rho_min
+    labels = fof_labels(t["x"], t["y"], t["z"], box, ll, select=select)
+    cat = fof_catalog(labels, t["x"], t["y"], t["z"], t["m"], box, min_members=args.min_members,
+                      v=(t["vx"], t["vy"], t["vz"]))
+    cols = [cat["label"].double(), cat["count"].double(), cat["mass"], *cat["com"].T, *cat["vel"].T]
+    table = torch.stack([c.cpu() for c in cols], dim=1).numpy() if cat["label"].numel() else np.zeros((0, 9))
+    out = args.out or "groups.txt"
+    np.savetxt(out, table, fmt=["%d", "%d"] + ["%.17e"] * 7,
+               header=f"label count mass cx cy cz vx vy vz  (linking length {ll:.17e}, min members {args.min_members})")
+    if args.labels:
+        np.save(args.labels, labels.cpu().numpy())
+    print(f"wrote {out}: {table.shape[0]} groups of at least {args.min_members} among {n} particles, linking length "
+          f"{ll:.6e}" + (f", largest {int(table[0, 1])} members" if table.shape[0] else ""))
+
+
 def cmd_substep_timings(args):
     """the profile file holds blocks: 'numRanks R numIterations K', a header of substep names, one row of times"""
     with open(args.profile) as fh:
@@ -380,6 +412,17 @@ def main(argv=None):
         p.add_argument("--res", type=int, default=128)
         p.add_argument("--device", default="cuda")
         p.add_argument("-o", "--out", default=None)
+    p = sub.add_parser("fof")
+    p.add_argument("file")
+    p.add_argument("-s", "--step", type=int, default=None)
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--b", type=float, default=0.2)
+    g.add_argument("--ll", type=float, default=None)
+    p.add_argument("--rho-min", type=float, default=None)
+    p.add_argument("--min-members", type=int, default=20)
+    p.add_argument("--device", default="cuda")
+    p.add_argument("-o", "--out", default=None)
+    p.add_argument("--labels", default=None)
     p = sub.add_parser("substep-timings")
     p.add_argument("profile")
     args, extra = ap.parse_known_args(argv)
@@ -389,7 +432,7 @@ def main(argv=None):
         if extra:
             ap.error(f"unrecognized arguments: {' '.join(extra)}")
         {"steps": cmd_steps, "add-m1": cmd_add_m1, "init-file": cmd_init_file, "radial-profile": cmd_radial_profile,
-         "slice": cmd_slice, "image": cmd_image, "volume": cmd_volume, "spectrum": cmd_spectrum,
+         "slice": cmd_slice, "image": cmd_image, "volume": cmd_volume, "spectrum": cmd_spectrum, "fof": cmd_fof,
          "substep-timings": cmd_substep_timings}[args.cmd](args)
     return 0
 
