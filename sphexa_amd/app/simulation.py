@@ -234,6 +234,34 @@ class Simulation:
                           v=(own("vx"), own("vy"), own("vz")))
         return labels, cat
 
+    def pair_statistics(self, edges, fields=("count",), rho_min: float | None = None, stride: int | None = None):
+        """pair counts and pair sums of the owned particles in the radial bins ``edges`` (ops/pairstats.py).
+        ``fields``: "mass" adds the mass-weighted counts ww, "velocity" the structure-function sums dl1, dl2, dl3 and
+        dv2 (a name or a sequence of names; "count" is always there). ``rho_min`` lets only the particles with
+        rho >= rho_min take part, ``stride`` only every stride-th owned particle. One rank only: pairs across ranks
+        are not formed"""
+        from ..ops.pairstats import pair_statistics
+
+        if self.comm.size > 1:
+            raise NotImplementedError("pair_statistics: pairs across ranks are not formed yet; run on one rank or "
+                                      "call it on a gathered snapshot (python -m sphexa_amd.tools pairs)")
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        if not set(fields) <= {"count", "mass", "velocity"}:
+            raise ValueError(f"pair_statistics: fields are count, mass and velocity, not {fields}")
+        d, box = self.d, self.domain.box
+        first, last = self.domain.start_index(), self.domain.end_index()
+        select = None
+        if rho_min is not None:
+            if not d.is_allocated("rho"):
+                raise ValueError("pair_statistics: rho_min needs the density field rho, which this run does not hold")
+            select = d["rho"] >= float(rho_min)
+        if stride is not None and int(stride) > 1:
+            every = (torch.arange(d["x"].numel(), device=d["x"].device) - first) % int(stride) == 0
+            select = every if select is None else select & every
+        return pair_statistics(d["x"], d["y"], d["z"], box, edges, w=d["m"] if "mass" in fields else None,
+                               v=(d["vx"], d["vy"], d["vz"]) if "velocity" in fields else None, select=select,
+                               first=first, last=last)
+
     def local(self, name):
         """field values of the locally owned particles"""
         return self.d[name][self.domain.start_index():self.domain.end_index()]

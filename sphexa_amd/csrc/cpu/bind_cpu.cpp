@@ -162,6 +162,19 @@ PYBIND11_MODULE(_sphx_cpu, m)
               cpu::fofLabels(np, P<double>(x), P<double>(y), P<double>(z), P<uint8_t>(select), toBox(box),
                              makeFofGrid(toBox(box), b, ext.data()), P<int32_t>(label));
           });
+    m.def("pair_statistics",
+          [](int64_t np, Ptr x, Ptr y, Ptr z, Ptr select, const BoxArr& box, const std::vector<double>& edges,
+             const std::array<double, 6>& ext, Ptr w, Ptr vx, Ptr vy, Ptr vz, double W,
+             const std::array<double, 3>& vrange, int64_t maxBound, Ptr out)
+          {
+              const FofGrid g = makePairGrid(toBox(box), edges.back(), ext.data());
+              std::array<double, 5> q;
+              const int64_t bound = cpu::pairStatistics(
+                  np, P<double>(x), P<double>(y), P<double>(z), P<uint8_t>(select), toBox(box), g,
+                  makePairTables(edges.data(), int(edges.size()) - 1, g), P<double>(w), P<float>(vx), P<float>(vy),
+                  P<float>(vz), W, vrange.data(), maxBound, q.data(), P<int64_t>(out));
+              return py::make_tuple(bound, q);
+          });
     m.def("fof_catalog",
           [](int64_t n, Ptr label, Ptr x, Ptr y, Ptr z, Ptr mm, Ptr vx, Ptr vy, Ptr vz, const BoxArr& box,
              int64_t minMembers)

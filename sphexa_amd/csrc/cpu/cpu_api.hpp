@@ -155,3 +155,18 @@ FofCatalog fofCatalog(int64_t n, const int32_t* label, const double* x, const do
                       int64_t minMembers);
 
 } // namespace sphx::cpu
+
+#include "sphx/pairstats.hpp"
+
+namespace sphx::cpu
+{
+
+//! pair statistics of np particles (ops/pairstats.py): select, w and vx, vy, vz may be null. out: kPairChannels rows
+//! of T.nb int64 (count, then the quantised sums), q: the 5 quanta. Returns the bound on the candidate pairs; more
+//! than maxBound of them: std::invalid_argument
+int64_t pairStatistics(int64_t np, const double* x, const double* y, const double* z, const uint8_t* select,
+                       const Box& box, const FofGrid& g, const PairTables& T, const double* w, const float* vx,
+                       const float* vy, const float* vz, double W, const double* vrange, int64_t maxBound, double* q,
+                       int64_t* out);
+
+} // namespace sphx::cpu

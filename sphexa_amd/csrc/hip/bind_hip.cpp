@@ -705,6 +705,38 @@ PYBIND11_MODULE(_sphx_hip, m)
                       P<double>(com), P<double>(vel), St(s));
           });
 
+    // ------------------------------------------------------------------------------------------- pair statistics
+    // sorted: x, y, z, w, v of PairSorted
+    auto pairSorted = [](const std::vector<Ptr>& b)
+    {
+        if (b.size() != 5) throw std::invalid_argument("pairstats: 5 sorted buffers");
+        return PairSorted{P<double>(b[0]), P<double>(b[1]), P<double>(b[2]), P<double>(b[3]), P<float4>(b[4])};
+    };
+    m.def("pair_prepare",
+          [fofBuffers, pairSorted](int64_t np, Ptr x, Ptr y, Ptr z, Ptr select, const BoxArr& box, double rmax,
+                                   const Ext6& ext, const std::vector<Ptr>& bufs, Ptr w, Ptr vx, Ptr vy, Ptr vz,
+                                   const std::vector<Ptr>& sorted, Ptr s)
+          {
+              pairPrepare(np, P<double>(x), P<double>(y), P<double>(z), P<uint8_t>(select),
+                          makePairGrid(toBox(box), rmax, ext.data()), fofBuffers(bufs), P<double>(w), P<float>(vx),
+                          P<float>(vy), P<float>(vz), pairSorted(sorted), St(s));
+          });
+    m.def("pair_run",
+          [fofBuffers, pairSorted](int64_t np, int64_t ns, int64_t ncells, int64_t nItems, int64_t pBound,
+                                   const BoxArr& box, const std::vector<double>& edges, const Ext6& ext, int channels,
+                                   double W, const std::array<double, 3>& vrange, const std::vector<Ptr>& bufs,
+                                   const std::vector<Ptr>& sorted, int variant, Ptr stats, Ptr out, Ptr s)
+          {
+              const FofGrid g = makePairGrid(toBox(box), edges.back(), ext.data());
+              std::array<double, 5> q;
+              pairQuanta(W, vrange.data(), pBound, q.data());
+              pairRun(np, ns, ncells, nItems, toBox(box), g, makePairTables(edges.data(), int(edges.size()) - 1, g),
+                      channels, q.data(), fofBuffers(bufs), pairSorted(sorted), variant,
+                      P<unsigned long long>(stats), P<int64_t>(out), St(s));
+              return q;
+          });
+    m.def("pair_replicas", &pairReplicas);
+
     // ------------------------------------------------------------------------------------------------ volumes
     using VolArr = std::array<double, 9>;
     using Res3   = std::array<int, 3>;
@@ -743,7 +775,7 @@ PYBIND11_MODULE(_sphx_hip, m)
           { spectrumShells(C, N, P<float>(spec), nbins, P<double>(partial), P<double>(out), St(s)); });
 
     m.def("device_check_flags",
-          []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume(); },
+          []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume() | dcheckPairstats(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");
     m.def("direct_sum",
           [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr mm, double G, Ptr ax, Ptr ay,

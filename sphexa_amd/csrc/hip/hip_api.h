@@ -12,6 +12,7 @@
 #include "sphx/cooling.hpp"
 #include "sphx/fof.hpp"
 #include "sphx/image.hpp"
+#include "sphx/pairstats.hpp"
 #include "sphx/sph_math.hpp"
 #include "sphx/volume.hpp"
 
@@ -403,6 +404,26 @@ void fofSums(int64_t n, int64_t Gall, int64_t G, const int32_t* perm2, const int
              const uint64_t* keysSorted, const double* x, const double* y, const double* z, const double* m,
              const double* vx, const double* vy, const double* vz, const Box& box, int32_t* label, int64_t* count,
              double* mass, double* com, double* vel, hipStream_t s);
+// pairstats.hip: pair counts and pair sums per radial bin (ops/pairstats.py holds the sequence: prepare, one read of the
+// counts, run). The grid is makePairGrid's, the buffers are those of fofPrepare, which the preparation runs
+struct PairSorted
+{
+    double *x, *y, *z, *w; // ns each, in sorted order (w: only with weights)
+    float4* v;             // ns (only with velocities)
+};
+//! fofPrepare, then counts[3] = bound on the candidate pairs, and the particle data in sorted order
+void pairPrepare(int64_t np, const double* x, const double* y, const double* z, const uint8_t* select,
+                 const FofGrid& g, const FofBuffers& B, const double* w, const float* vx, const float* vy,
+                 const float* vz, const PairSorted& S, hipStream_t s);
+//! the pair kernel: adds to out (kPairChannels rows of nb int64, zeroed by the caller). channels: kPairWeights |
+//! kPairVelocity; q: the 5 quanta (pairQuanta); variant 0: replicated LDS histogram, 1: ballot per distinct bin;
+//! stats (may be null): 3 zeroed counters, see pairstats.hip PairArgs
+void pairRun(int64_t np, int64_t ns, int64_t ncells, int64_t nItems, const Box& box, const FofGrid& g,
+             const PairTables& t, int channels, const double* q, const FofBuffers& B, const PairSorted& S, int variant,
+             unsigned long long* stats, int64_t* out, hipStream_t s);
+//! replicas of the per-wave histogram at nb bins and a channel set
+int pairReplicas(int nb, int channels);
+unsigned dcheckPairstats();
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
                          const double* z, unsigned long long* stats, void* scratch, int testFrontCap, int capM,

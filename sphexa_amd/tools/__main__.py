@@ -22,6 +22,9 @@ Commands:
                                               shell-binned power spectrum of the interpolated fields: k, P, count
   fof FILE [-s STEP] [--b 0.2 | --ll L] [--rho-min R] [--min-members 20] [--device cuda] [-o groups.txt]
       [--labels labels.npy]                   friends-of-friends groups (ops/fof.py): label count mass cx cy cz vx vy vz
+  pairs FILE [-s STEP] --rmin A --rmax B --bins N [--log] [--velocity] [--mass] [--stride K] [--device cuda]
+      [-o pairs.txt]                          pair counts per radial bin (ops/pairstats.py): r_lo r_hi count [ww]
+                                              [S2L S2T S3L] [xi]
   substep-timings PROFILE
 """
 
@@ -343,6 +346,40 @@ def cmd_fof(args):
           f"{ll:.6e}" + (f", largest {int(table[0, 1])} members" if table.shape[0] else ""))
 
 
+def cmd_pairs(args):
+    """pair counts of a step in ``--bins`` linear or logarithmic radial bins between ``--rmin`` and ``--rmax`` as text
+    columns; ``--mass`` adds the mass-weighted counts, ``--velocity`` the structure functions, and a fully periodic box
+    the two-point correlation function xi"""
+    import torch
+
+    from ..ops.pairstats import correlation_function, pair_statistics, structure_functions
+
+    _, box = _step_box(args)
+    d = _read(args.file, args.step, ["x", "y", "z"] + (["m"] if args.mass else []) +
+              (["vx", "vy", "vz"] if args.velocity else []))
+    dev = torch.device(args.device)
+    t = {k: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev) for k, a in d.items()}
+    n = t["x"].numel()
+    edges = (np.geomspace if args.log else np.linspace)(args.rmin, args.rmax, args.bins + 1)
+    select = None if args.stride <= 1 else torch.arange(n, device=dev) % args.stride == 0
+    stats = pair_statistics(t["x"], t["y"], t["z"], box, edges, w=t["m"] if args.mass else None,
+                            v=(t["vx"], t["vy"], t["vz"]) if args.velocity else None, select=select)
+    e = torch.as_tensor(edges)
+    names, cols = ["r_lo", "r_hi", "count"], [e[:-1], e[1:], stats["count"].double()]
+    if args.mass:
+        names, cols = names + ["ww"], cols + [stats["ww"]]
+    if args.velocity:
+        sf = structure_functions(stats)
+        names, cols = names + ["S2L", "S2T", "S3L"], cols + [sf["S2L"], sf["S2T"], sf["S3L"]]
+    if all(bc == 1 for bc in box.bc):
+        taking_part = n if select is None else int(select.sum())
+        names, cols = names + ["xi"], cols + [correlation_function(stats, edges, taking_part, box)]
+    out = args.out or "pairs.txt"
+    np.savetxt(out, torch.stack([c.cpu() for c in cols], dim=1).numpy(), fmt="%.17e",
+               header=" ".join(names) + f"  ({stats['pairs_bound']} candidate pairs)")
+    print(f"wrote {out}: {int(stats['count'].sum())} pairs of {n} particles in {args.bins} bins")
+
+
 def cmd_substep_timings(args):
     """the profile file holds blocks: 'numRanks R numIterations K', a header of substep names, one row of times"""
     with open(args.profile) as fh:
@@ -423,6 +460,18 @@ def main(argv=None):
     p.add_argument("--device", default="cuda")
     p.add_argument("-o", "--out", default=None)
     p.add_argument("--labels", default=None)
+    p = sub.add_parser("pairs")
+    p.add_argument("file")
+    p.add_argument("-s", "--step", type=int, default=None)
+    p.add_argument("--rmin", type=float, required=True)
+    p.add_argument("--rmax", type=float, required=True)
+    p.add_argument("--bins", type=int, required=True)
+    p.add_argument("--log", action="store_true")
+    p.add_argument("--velocity", action="store_true")
+    p.add_argument("--mass", action="store_true")
+    p.add_argument("--stride", type=int, default=1)
+    p.add_argument("--device", default="cuda")
+    p.add_argument("-o", "--out", default=None)
     p = sub.add_parser("substep-timings")
     p.add_argument("profile")
     args, extra = ap.parse_known_args(argv)
@@ -433,7 +482,7 @@ def main(argv=None):
             ap.error(f"unrecognized arguments: {' '.join(extra)}")
         {"steps": cmd_steps, "add-m1": cmd_add_m1, "init-file": cmd_init_file, "radial-profile": cmd_radial_profile,
          "slice": cmd_slice, "image": cmd_image, "volume": cmd_volume, "spectrum": cmd_spectrum, "fof": cmd_fof,
-         "substep-timings": cmd_substep_timings}[args.cmd](args)
+         "pairs": cmd_pairs, "substep-timings": cmd_substep_timings}[args.cmd](args)
     return 0
 
 
