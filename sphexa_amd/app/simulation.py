@@ -209,10 +209,15 @@ class Simulation:
         return power_spectrum(u.contiguous())
 
     def find_groups(self, b: float = 0.2, linking_length: float | None = None, rho_min: float | None = None,
-                    min_members: int = 20):
+                    min_members: int = 20, bound: bool = False, eps: float | None = None,
+                    use_internal_energy: bool = False):
         """friends-of-friends groups of the owned particles (ops/fof.py): (labels, catalogue). The linking length
         defaults to ``b`` mean particle spacings, b (V_box / N_total)^(1/3); ``rho_min`` lets only the particles with
-        rho >= rho_min take part. One rank only: groups are not merged across ranks"""
+        rho >= rho_min take part. One rank only: groups are not merged across ranks.
+        ``bound``: the groups are unbound as well (ops/groups.py, with the run's gravitational constant, the Plummer
+        softening ``eps``, by default 0.1 linking lengths, and, with ``use_internal_energy``, u in the energies):
+        (labels, catalogue, bound), the catalogue with the bound quantities added (the bulk velocity of the bound
+        members as ``bound_vel``; ``vel`` stays the mean velocity of all members)"""
         from ..ops.fof import fof_catalog, fof_labels
 
         if self.comm.size > 1:
@@ -232,7 +237,20 @@ class Simulation:
         own = lambda name: d[name][first:last]
         cat = fof_catalog(labels, own("x"), own("y"), own("z"), own("m"), box, min_members=min_members,
                           v=(own("vx"), own("vy"), own("vz")))
-        return labels, cat
+        if not bound:
+            return labels, cat
+        from ..ops.groups import bound_groups
+
+        if d.g == 0.0:
+            raise ValueError("find_groups: bound groups need self-gravity, and this run has G = 0")
+        if use_internal_energy and not d.is_allocated("u"):
+            raise ValueError("find_groups: use_internal_energy needs the field u, which this run does not hold")
+        mask, _, bcat = bound_groups(labels, own("x"), own("y"), own("z"), own("m"),
+                                     (own("vx"), own("vy"), own("vz")), box,
+                                     0.1 * linking_length if eps is None else eps, G=d.g,
+                                     u=own("u") if use_internal_energy else None, min_members=min_members)
+        bcat["bound_vel"] = bcat.pop("vel")
+        return labels, {**bcat, **cat}, mask
 
     def pair_statistics(self, edges, fields=("count",), rho_min: float | None = None, stride: int | None = None):
         """pair counts and pair sums of the owned particles in the radial bins ``edges`` (ops/pairstats.py).

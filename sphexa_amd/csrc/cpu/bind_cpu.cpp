@@ -184,6 +184,17 @@ PYBIND11_MODULE(_sphx_cpu, m)
               return py::make_tuple(toNumpy(c.label), toNumpy(c.count), toNumpy(c.sums));
           });
 
+    m.def("bound_groups",
+          [](int64_t n, Ptr label, Ptr x, Ptr y, Ptr z, Ptr mm, Ptr vx, Ptr vy, Ptr vz, Ptr u, const BoxArr& box,
+             double eps, double G, int64_t minMembers, int maxIter, Ptr bound, Ptr phi)
+          {
+              auto c = cpu::boundGroups(n, P<int32_t>(label), P<double>(x), P<double>(y), P<double>(z), P<double>(mm),
+                                        P<double>(vx), P<double>(vy), P<double>(vz), P<double>(u), toBox(box), eps, G,
+                                        minMembers, maxIter, P<uint8_t>(bound), P<double>(phi));
+              return py::make_tuple(c.iterations, toNumpy(c.boundCount), toNumpy(c.sums), toNumpy(c.centreIndex),
+                                    toNumpy(c.mostBound));
+          });
+
     m.def("compute_keys", [](int64_t n, Ptr x, Ptr y, Ptr z, const BoxArr& box, int kind, Ptr keys)
           { cpu::computeKeys(n, P<double>(x), P<double>(y), P<double>(z), toBox(box), kind, P<KeyT>(keys)); });
 

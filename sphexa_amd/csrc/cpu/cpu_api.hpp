@@ -156,6 +156,28 @@ FofCatalog fofCatalog(int64_t n, const int32_t* label, const double* x, const do
 
 } // namespace sphx::cpu
 
+#include "sphx/groups.hpp"
+
+namespace sphx::cpu
+{
+
+//! bound groups (ops/groups.py): per group of at least minMembers, in catalogue order, the bound count, 10 sums
+//! {bound mass, vel, ekin, eint, epot, centre} and the particles behind the centre and of lowest e
+struct BoundGroups
+{
+    int iterations;
+    std::vector<int64_t> boundCount;
+    std::vector<double> sums;
+    std::vector<int32_t> centreIndex, mostBound;
+};
+//! u may be null; bound and phiOut (n each) are written for every particle (0 and NaN where not a bound member)
+BoundGroups boundGroups(int64_t n, const int32_t* label, const double* x, const double* y, const double* z,
+                        const double* m, const double* vx, const double* vy, const double* vz, const double* u,
+                        const Box& box, double eps, double Gc, int64_t minMembers, int maxIter, uint8_t* bound,
+                        double* phiOut);
+
+} // namespace sphx::cpu
+
 #include "sphx/pairstats.hpp"
 
 namespace sphx::cpu

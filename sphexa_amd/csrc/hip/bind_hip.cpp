@@ -705,6 +705,56 @@ PYBIND11_MODULE(_sphx_hip, m)
                       P<double>(com), P<double>(vel), St(s));
           });
 
+    // ---------------------------------------------------------------------------------------------- bound groups
+    // bufs: the fields of GroupBuffers in their order (tmpBytes last, as a number); fields: m, vx, vy, vz, u
+    auto groupBuffers = [](const std::vector<Ptr>& b)
+    {
+        if (b.size() != 17) throw std::invalid_argument("groups: 17 buffer entries");
+        return GroupBuffers{{P<float4>(b[0]), P<float4>(b[1])},   {P<int32_t>(b[2]), P<int32_t>(b[3])},
+                            {P<int32_t>(b[4]), P<int32_t>(b[5])}, P<int64_t>(b[6]),  P<int64_t>(b[7]),
+                            P<int64_t>(b[8]),  P<int64_t>(b[9]),  P<int64_t>(b[10]), P<int64_t>(b[11]),
+                            P<double>(b[12]),  P<double>(b[13]),  P<double>(b[14]),  P<void>(b[15]), size_t(b[16])};
+    };
+    auto groupFields = [](const std::vector<Ptr>& f)
+    {
+        if (f.size() != 5) throw std::invalid_argument("groups: 5 fields");
+        return GroupFields4{P<double>(f[0]), P<double>(f[1]), P<double>(f[2]), P<double>(f[3]), P<double>(f[4])};
+    };
+    m.def("group_tile", &groupTile);
+    m.def("group_init",
+          [groupBuffers](int64_t n, int64_t Gall, int64_t G, int seg, Ptr perm2, Ptr gstart,
+                         const std::vector<Ptr>& bufs, Ptr s)
+          { groupInit(n, Gall, G, seg, P<int32_t>(perm2), P<int32_t>(gstart), groupBuffers(bufs), St(s)); });
+    m.def("group_members",
+          [groupBuffers](int64_t n, int64_t Gall, int64_t G, int64_t M, Ptr perm2, Ptr gstart, Ptr perm, Ptr x, Ptr y,
+                         Ptr z, Ptr mm, const BoxArr& box, const std::vector<Ptr>& bufs, Ptr s)
+          {
+              groupMembers(n, Gall, G, M, P<int32_t>(perm2), P<int32_t>(gstart), P<int32_t>(perm), P<double>(x),
+                           P<double>(y), P<double>(z), P<double>(mm), toBox(box), groupBuffers(bufs), St(s));
+          });
+    m.def("group_evaluate",
+          [groupBuffers, groupFields](int64_t n, int64_t G, int64_t M, int64_t nItems, int64_t nPartial, int seg,
+                                      int cur, double eps, double Gc, const std::vector<Ptr>& fields,
+                                      const std::vector<Ptr>& bufs, Ptr partial, Ptr s)
+          {
+              groupEvaluate(n, G, M, nItems, nPartial, seg, cur, eps, Gc, groupFields(fields), groupBuffers(bufs),
+                            P<double>(partial), St(s));
+          });
+    m.def("group_remove",
+          [groupBuffers](int64_t n, int64_t G, int64_t M, int64_t minMembers, int seg, int cur,
+                         const std::vector<Ptr>& bufs, Ptr s)
+          { groupRemove(n, G, M, minMembers, seg, cur, groupBuffers(bufs), St(s)); });
+    m.def("group_catalog",
+          [groupBuffers, groupFields](int64_t n, int64_t G, int64_t M, int cur, Ptr x, Ptr y, Ptr z,
+                                      const std::vector<Ptr>& fields, const BoxArr& box, const std::vector<Ptr>& bufs,
+                                      Ptr boundCount, Ptr sums, Ptr centreIndex, Ptr mostBound, Ptr bound, Ptr phiOut,
+                                      Ptr s)
+          {
+              groupCatalog(n, G, M, cur, P<double>(x), P<double>(y), P<double>(z), groupFields(fields), toBox(box),
+                           groupBuffers(bufs), P<int64_t>(boundCount), P<double>(sums), P<int32_t>(centreIndex),
+                           P<int32_t>(mostBound), P<uint8_t>(bound), P<double>(phiOut), St(s));
+          });
+
     // ------------------------------------------------------------------------------------------- pair statistics
     // sorted: x, y, z, w, v of PairSorted
     auto pairSorted = [](const std::vector<Ptr>& b)
@@ -775,7 +825,8 @@ PYBIND11_MODULE(_sphx_hip, m)
           { spectrumShells(C, N, P<float>(spec), nbins, P<double>(partial), P<double>(out), St(s)); });
 
     m.def("device_check_flags",
-          []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume() | dcheckPairstats(); },
+          []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume() | dcheckPairstats() |
+                        dcheckGroups(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");
     m.def("direct_sum",
           [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr mm, double G, Ptr ax, Ptr ay,

@@ -11,6 +11,7 @@
 #include "sphx/box.hpp"
 #include "sphx/cooling.hpp"
 #include "sphx/fof.hpp"
+#include "sphx/groups.hpp"
 #include "sphx/image.hpp"
 #include "sphx/pairstats.hpp"
 #include "sphx/sph_math.hpp"
@@ -404,6 +405,45 @@ void fofSums(int64_t n, int64_t Gall, int64_t G, const int32_t* perm2, const int
              const uint64_t* keysSorted, const double* x, const double* y, const double* z, const double* m,
              const double* vx, const double* vy, const double* vz, const Box& box, int32_t* label, int64_t* count,
              double* mass, double* com, double* vel, hipStream_t s);
+// groups.hip: self-potential and unbinding of friends-of-friends groups (sphx/groups.hpp; ops/groups.py holds the
+// sequence: fofGroups, init, one read, members, then per iteration evaluate, remove, one read; at last the catalogue)
+struct GroupBuffers
+{
+    float4* rec[2];              // M each: the two sets of compact member arrays (a removal writes the other set)
+    int32_t *idx[2], *grp[2];    // M each
+    int64_t *bcount, *bstart, *itemOff, *partOff; // G, then G + 1 each
+    int64_t* scan;               // M + 1
+    int64_t* counters;           // 4: members removed (zeroed by the caller before groupRemove), items, doubles of
+                                 // partial rows, bound members
+    double *phi, *e, *Vg;        // M, M, 4 G
+    void* tmp;                   // the scan's workspace for max(G, M) + 1 elements
+    size_t tmpBytes;
+};
+struct GroupFields4
+{
+    const double *m, *vx, *vy, *vz, *u; // by particle; u may be null
+};
+//! members per target tile of the potential kernel
+int groupTile();
+//! bound counts = member counts of the first G groups in the order perm2, and the plan (starts, items, partial rows)
+void groupInit(int64_t n, int64_t Gall, int64_t G, int seg, const int32_t* perm2, const int32_t* gstart,
+               const GroupBuffers& B, hipStream_t s);
+//! the compact member arrays (set 0) of the M members
+void groupMembers(int64_t n, int64_t Gall, int64_t G, int64_t M, const int32_t* perm2, const int32_t* gstart,
+                  const int32_t* perm, const double* x, const double* y, const double* z, const double* m,
+                  const Box& box, const GroupBuffers& B, hipStream_t s);
+//! phi, the bulk velocities and e of the bound members in set cur; partial: nPartial doubles (null if 0)
+void groupEvaluate(int64_t n, int64_t G, int64_t M, int64_t nItems, int64_t nPartial, int seg, int cur, double eps,
+                   double Gc, const GroupFields4& f, const GroupBuffers& B, double* partial, hipStream_t s);
+//! removes e > 0, dissolves groups below minMembers, compacts set cur into the other set and plans the next iteration
+void groupRemove(int64_t n, int64_t G, int64_t M, int64_t minMembers, int seg, int cur, const GroupBuffers& B,
+                 hipStream_t s);
+//! per group: bound count, 10 sums {bound mass, vel, ekin, eint, epot, centre}, the particles behind the centre and
+//! of lowest e; per particle: bound (zeroed by the caller) and phi (NaN-filled by the caller)
+void groupCatalog(int64_t n, int64_t G, int64_t M, int cur, const double* x, const double* y, const double* z,
+                  const GroupFields4& f, const Box& box, const GroupBuffers& B, int64_t* boundCount, double* sums,
+                  int32_t* centreIndex, int32_t* mostBound, uint8_t* bound, double* phiOut, hipStream_t s);
+unsigned dcheckGroups();
 // pairstats.hip: pair counts and pair sums per radial bin (ops/pairstats.py holds the sequence: prepare, one read of the
 // counts, run). The grid is makePairGrid's, the buffers are those of fofPrepare, which the preparation runs
 struct PairSorted

@@ -22,6 +22,9 @@ Commands:
                                               shell-binned power spectrum of the interpolated fields: k, P, count
   fof FILE [-s STEP] [--b 0.2 | --ll L] [--rho-min R] [--min-members 20] [--device cuda] [-o groups.txt]
       [--labels labels.npy]                   friends-of-friends groups (ops/fof.py): label count mass cx cy cz vx vy vz
+      [--bound [--eps E] [--G g] [--max-iter K] [--thermal] [--bound-mask FILE.npy]]
+                                              unbinds the groups (ops/groups.py; eps defaults to 0.1 linking lengths) and
+                                              adds: bound_count bound_mass bvx bvy bvz ekin eint epot px py pz most_bound
   pairs FILE [-s STEP] --rmin A --rmax B --bins N [--log] [--velocity] [--mass] [--stride K] [--device cuda]
       [-o pairs.txt]                          pair counts per radial bin (ops/pairstats.py): r_lo r_hi count [ww]
                                               [S2L S2T S3L] [xi]
@@ -324,7 +327,8 @@ def cmd_fof(args):
     from ..ops.fof import fof_catalog, fof_labels
 
     _, box = _step_box(args)
-    names = ["x", "y", "z", "m", "vx", "vy", "vz"] + (["rho"] if args.rho_min is not None else [])
+    names = ["x", "y", "z", "m", "vx", "vy", "vz"] + (["rho"] if args.rho_min is not None else []) + \
+        (["u"] if args.thermal else [])
     d = _read(args.file, args.step, names)
     dev = torch.device(args.device)
     t = {k: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev) for k, a in d.items()}
@@ -336,10 +340,22 @@ def cmd_fof(args):
     cat = fof_catalog(labels, t["x"], t["y"], t["z"], t["m"], box, min_members=args.min_members,
                       v=(t["vx"], t["vy"], t["vz"]))
     cols = [cat["label"].double(), cat["count"].double(), cat["mass"], *cat["com"].T, *cat["vel"].T]
-    table = torch.stack([c.cpu() for c in cols], dim=1).numpy() if cat["label"].numel() else np.zeros((0, 9))
+    fmt, head = ["%d", "%d"] + ["%.17e"] * 7, "label count mass cx cy cz vx vy vz"
+    if args.bound:
+        from ..ops.groups import bound_groups
+
+        mask, _, bc = bound_groups(labels, t["x"], t["y"], t["z"], t["m"], (t["vx"], t["vy"], t["vz"]), box,
+                                   0.1 * ll if args.eps is None else args.eps, G=args.G, u=t.get("u"),
+                                   min_members=args.min_members, max_iter=args.max_iter)
+        cols += [bc["bound_count"].double(), bc["bound_mass"], *bc["vel"].T, bc["ekin"], bc["eint"], bc["epot"],
+                 *bc["centre"].T, bc["most_bound"].double()]
+        fmt += ["%d"] + ["%.17e"] * 10 + ["%d"]
+        head += f" bound_count bound_mass bvx bvy bvz ekin eint epot px py pz most_bound  ({bc['iterations']} iterations)"
+        if args.bound_mask:
+            np.save(args.bound_mask, mask.cpu().numpy())
+    table = torch.stack([c.cpu() for c in cols], dim=1).numpy() if cat["label"].numel() else np.zeros((0, len(fmt)))
     out = args.out or "groups.txt"
-    np.savetxt(out, table, fmt=["%d", "%d"] + ["%.17e"] * 7,
-               header=f"label count mass cx cy cz vx vy vz  (linking length {ll:.17e}, min members {args.min_members})")
+    np.savetxt(out, table, fmt=fmt, header=f"{head}  (linking length {ll:.17e}, min members {args.min_members})")
     if args.labels:
         np.save(args.labels, labels.cpu().numpy())
     print(f"wrote {out}: {table.shape[0]} groups of at least {args.min_members} among {n} particles, linking length "
@@ -460,6 +476,12 @@ def main(argv=None):
     p.add_argument("--device", default="cuda")
     p.add_argument("-o", "--out", default=None)
     p.add_argument("--labels", default=None)
+    p.add_argument("--bound", action="store_true")
+    p.add_argument("--eps", type=float, default=None)
+    p.add_argument("--G", type=float, default=1.0)
+    p.add_argument("--max-iter", type=int, default=20)
+    p.add_argument("--thermal", action="store_true")
+    p.add_argument("--bound-mask", default=None)
     p = sub.add_parser("pairs")
     p.add_argument("file")
     p.add_argument("-s", "--step", type=int, default=None)
