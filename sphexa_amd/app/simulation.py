@@ -252,6 +252,31 @@ class Simulation:
         bcat["bound_vel"] = bcat.pop("vel")
         return labels, {**bcat, **cat}, mask
 
+    def group_profiles(self, catalogue, edges, overdensity=(200.0,), reference="mean", centre: str = "centre"):
+        """radial profiles and spherical-overdensity masses (ops/profiles.py) of the owned particles about the groups
+        of a ``find_groups`` catalogue, in the radial bins ``edges``. Centres are ``catalogue[centre]`` (``com`` where
+        that is NaN or absent), the centre velocities ``bound_vel`` (``vel`` where that is NaN or absent), the
+        thresholds ``overdensity`` times the reference density: ``reference`` = "mean", the owned mass over the box
+        volume, or a number. One rank only: spheres are not merged across ranks"""
+        from ..ops.profiles import radial_profiles
+
+        if self.comm.size > 1:
+            raise NotImplementedError("group_profiles: groups are not merged across ranks yet; run on one rank or "
+                                      "call it on a gathered snapshot (python -m sphexa_amd.tools fof)")
+        d, box = self.d, self.domain.box
+        first, last = self.domain.start_index(), self.domain.end_index()
+        pick = lambda name, other: other if catalogue.get(name) is None else \
+            torch.where(torch.isnan(catalogue[name]), other, catalogue[name])
+        cen = pick(centre, catalogue["com"]).to(torch.float64).contiguous()
+        vc = pick("bound_vel", catalogue["vel"]).to(torch.float64).contiguous()
+        if reference == "mean":
+            lx, ly, lz = box.lengths()
+            reference = float(d["m"][first:last].sum(dtype=torch.float64)) / (lx * ly * lz)
+        thresholds = [float(o) * float(reference) for o in overdensity]
+        return radial_profiles(cen, d["x"], d["y"], d["z"], d["m"], box, edges, v=(d["vx"], d["vy"], d["vz"]),
+                               u=d["u"] if d.is_allocated("u") else None, vc=vc, thresholds=thresholds, first=first,
+                               last=last)
+
     def pair_statistics(self, edges, fields=("count",), rho_min: float | None = None, stride: int | None = None):
         """pair counts and pair sums of the owned particles in the radial bins ``edges`` (ops/pairstats.py).
         ``fields``: "mass" adds the mass-weighted counts ww, "velocity" the structure-function sums dl1, dl2, dl3 and

@@ -175,6 +175,19 @@ PYBIND11_MODULE(_sphx_cpu, m)
                   P<float>(vz), W, vrange.data(), maxBound, q.data(), P<int64_t>(out));
               return py::make_tuple(bound, q);
           });
+    m.def("radial_profiles",
+          [](int64_t C, Ptr cxyz, Ptr vc, int64_t np, Ptr x, Ptr y, Ptr z, Ptr select, Ptr mm, Ptr vx, Ptr vy, Ptr vz,
+             Ptr u, const BoxArr& box, const std::vector<double>& edges, const std::array<double, 6>& ext,
+             const std::vector<double>& rho, Ptr count, Ptr sums, Ptr soR, Ptr soM, Ptr soN, Ptr soTrunc, Ptr hits)
+          {
+              const FofGrid g = makePairGrid(toBox(box), edges.back(), ext.data());
+              cpu::radialProfiles(C, P<double>(cxyz), P<double>(vc), np, P<double>(x), P<double>(y), P<double>(z),
+                                  P<uint8_t>(select), P<double>(mm), P<double>(vx), P<double>(vy), P<double>(vz),
+                                  P<double>(u), toBox(box), g,
+                                  makeProfileTables(edges.data(), int(edges.size()) - 1, g), int(rho.size()),
+                                  rho.data(), P<int64_t>(count), P<double>(sums), P<double>(soR), P<double>(soM),
+                                  P<int64_t>(soN), P<uint8_t>(soTrunc), P<int64_t>(hits));
+          });
     m.def("fof_catalog",
           [](int64_t n, Ptr label, Ptr x, Ptr y, Ptr z, Ptr mm, Ptr vx, Ptr vy, Ptr vz, const BoxArr& box,
              int64_t minMembers)

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "sphx/box.hpp"
+#include "sphx/profiles.hpp"
 #include "sphx/sph_math.hpp"
 
 namespace sphx::cpu
@@ -190,5 +191,14 @@ int64_t pairStatistics(int64_t np, const double* x, const double* y, const doubl
                        const Box& box, const FofGrid& g, const PairTables& T, const double* w, const float* vx,
                        const float* vy, const float* vz, double W, const double* vrange, int64_t maxBound, double* q,
                        int64_t* out);
+
+//! radial profiles and spherical-overdensity masses about C centres (ops/profiles.py): vc, select, vx, vy, vz and u may
+//! be null. count (C x nb) and sums (5 rows of C x nb: mass, mvr, mvr2, mv2, mu) are added to (zeroed by the caller);
+//! soR, soM, soN, soTrunc are C x nt, hits is C. More than 2^31 - 1 hits: std::invalid_argument
+void radialProfiles(int64_t C, const double* cxyz, const double* vc, int64_t np, const double* x, const double* y,
+                    const double* z, const uint8_t* select, const double* m, const double* vx, const double* vy,
+                    const double* vz, const double* u, const Box& box, const FofGrid& g, const ProfileTables& T, int nt,
+                    const double* rho, int64_t* count, double* sums, double* soR, double* soM, int64_t* soN,
+                    uint8_t* soTrunc, int64_t* hits);
 
 } // namespace sphx::cpu

@@ -787,6 +787,56 @@ PYBIND11_MODULE(_sphx_hip, m)
           });
     m.def("pair_replicas", &pairReplicas);
 
+    // -------------------------------------------------------------------------------------------------- profiles
+    // pbufs: the fields of ProfileBuffers in their order (tmpBytes last, as a number)
+    auto profileBuffers = [](const std::vector<Ptr>& b)
+    {
+        if (b.size() != 6) throw std::invalid_argument("profiles: 6 buffer entries");
+        return ProfileBuffers{P<ProfileCentre>(b[0]), P<int32_t>(b[1]), P<int32_t>(b[2]),
+                              P<int64_t>(b[3]),       P<void>(b[4]),    size_t(b[5])};
+    };
+    m.def("profile_plan",
+          [fofBuffers, profileBuffers](int64_t C, int64_t np, Ptr cxyz, const BoxArr& box, double rmax, const Ext6& ext,
+                                       int seg, const std::vector<Ptr>& bufs, const std::vector<Ptr>& pbufs, Ptr s)
+          {
+              profilePlan(C, np, P<double>(cxyz), makePairGrid(toBox(box), rmax, ext.data()), seg, fofBuffers(bufs),
+                          profileBuffers(pbufs), St(s));
+          });
+    m.def("profile_hits",
+          [fofBuffers, pairSorted, profileBuffers](bool write, int64_t C, int64_t ns, int64_t nItems, int64_t H,
+                                                   Ptr cxyz, const BoxArr& box, const std::vector<double>& edges,
+                                                   const Ext6& ext, int seg, const std::vector<Ptr>& bufs,
+                                                   const std::vector<Ptr>& sorted, const std::vector<Ptr>& pbufs,
+                                                   Ptr itemHits, Ptr keys, Ptr pidx, Ptr stats, Ptr s)
+          {
+              const FofGrid g = makePairGrid(toBox(box), edges.back(), ext.data());
+              profileHits(write, C, ns, nItems, H, P<double>(cxyz), toBox(box), g,
+                          makeProfileTables(edges.data(), int(edges.size()) - 1, g), seg, fofBuffers(bufs),
+                          pairSorted(sorted), profileBuffers(pbufs), P<int64_t>(itemHits), P<uint64_t>(keys),
+                          P<int32_t>(pidx), P<unsigned long long>(stats), St(s));
+          });
+    m.def("profile_max_segments", &profileMaxSegments);
+    // fields: m, vx, vy, vz, u; work and out: the fields of ProfileWork and ProfileOut in their order
+    m.def("profile_reduce",
+          [pairSorted](int64_t C, int64_t H, int64_t np, int64_t ns, const BoxArr& box, const std::vector<double>& edges,
+                       const Ext6& ext, const std::vector<double>& rho, int seg, Ptr keysSorted, Ptr hperm, Ptr pidx,
+                       Ptr perm, const std::vector<Ptr>& sorted, const std::vector<Ptr>& f, Ptr cxyz, Ptr vc,
+                       const std::vector<Ptr>& w, const std::vector<Ptr>& o, Ptr tmp, size_t tmpBytes, Ptr s)
+          {
+              if (f.size() != 5 || w.size() != 8 || o.size() != 7)
+                  throw std::invalid_argument("profiles: 5 fields, 8 work arrays, 7 outputs");
+              const FofGrid g = makePairGrid(toBox(box), edges.back(), ext.data());
+              const ProfileFields F{P<double>(f[0]), P<double>(f[1]), P<double>(f[2]), P<double>(f[3]), P<double>(f[4])};
+              const ProfileWork W{P<int64_t>(w[0]), P<int64_t>(w[1]), P<double>(w[2]),  P<double>(w[3]),
+                                  P<double>(w[4]),  P<double>(w[5]),  P<int64_t>(w[6]), P<double>(w[7])};
+              const ProfileOut O{P<int64_t>(o[0]), P<double>(o[1]),  P<double>(o[2]), P<double>(o[3]),
+                                 P<int64_t>(o[4]), P<uint8_t>(o[5]), P<int64_t>(o[6])};
+              profileReduce(C, H, np, ns, toBox(box), makeProfileTables(edges.data(), int(edges.size()) - 1, g),
+                            int(rho.size()), rho.data(), seg, P<uint64_t>(keysSorted), P<int32_t>(hperm),
+                            P<int32_t>(pidx), P<int32_t>(perm), pairSorted(sorted), F, P<double>(cxyz), P<double>(vc),
+                            W, O, P<void>(tmp), tmpBytes, St(s));
+          });
+
     // ------------------------------------------------------------------------------------------------ volumes
     using VolArr = std::array<double, 9>;
     using Res3   = std::array<int, 3>;
@@ -826,7 +876,7 @@ PYBIND11_MODULE(_sphx_hip, m)
 
     m.def("device_check_flags",
           []() { return dcheckHydro() | dcheckSfc() | dcheckGravity() | dcheckImage() | dcheckVolume() | dcheckPairstats() |
-                        dcheckGroups(); },
+                        dcheckGroups() | dcheckProfiles(); },
           "read and clear the failed device-check bits (always 0 unless built with SPHX_DEVICE_CHECKS)");
     m.def("direct_sum",
           [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr mm, double G, Ptr ax, Ptr ay,

@@ -14,6 +14,7 @@
 #include "sphx/groups.hpp"
 #include "sphx/image.hpp"
 #include "sphx/pairstats.hpp"
+#include "sphx/profiles.hpp"
 #include "sphx/sph_math.hpp"
 #include "sphx/volume.hpp"
 
@@ -464,6 +465,56 @@ void pairRun(int64_t np, int64_t ns, int64_t ncells, int64_t nItems, const Box& 
 //! replicas of the per-wave histogram at nb bins and a channel set
 int pairReplicas(int nb, int channels);
 unsigned dcheckPairstats();
+// profiles.hip: radial profiles and spherical-overdensity masses about many centres (ops/profiles.py holds the
+// sequence: pairPrepare, plan, one read of the counts, hit count pass, one read of the hit count, hit write pass, a
+// sort of the hit keys, reduce). The grid is makePairGrid's, the buffers are those of pairPrepare
+struct ProfileBuffers
+{
+    ProfileCentre* crec;      // C
+    int32_t *slotLo, *slotHi; // C * kProfileSlots each
+    int64_t* itemOff;         // C * kProfileSlots + 1
+    void* tmp;                // the scan's workspace for max(C * kProfileSlots, items) + 1 elements
+    size_t tmpBytes;
+};
+struct ProfileFields
+{
+    const double *m, *vx, *vy, *vz, *u; // by particle; v and u may be null
+};
+struct ProfileWork
+{
+    int64_t *start, *segOff;           // C + 1 each
+    double *partial, *segMass, *carry; // U = profileMaxSegments rows of kProfileChannels * nb; U; U
+    double* hmass;                     // H
+    int64_t* segQ;                     // U * kProfileMaxThresholds
+    double* segM;                      // U * kProfileMaxThresholds
+};
+struct ProfileOut
+{
+    int64_t* count;   // C * nb
+    double* sums;     // 5 rows (mass, mvr, mvr2, mv2, mu) of C * nb
+    double *soR, *soM; // C * T
+    int64_t* soN;
+    uint8_t* soTrunc;
+    int64_t* hits;    // C
+};
+//! the centres' records, the sorted ranges of their slots and the item offsets; itemOff[C * kProfileSlots] = items
+void profilePlan(int64_t C, int64_t np, const double* cxyz, const FofGrid& g, int seg, const FofBuffers& B,
+                 const ProfileBuffers& P, hipStream_t s);
+//! the hit kernel. Count pass (write false): itemHits (nItems + 1) gets the items' offsets, the last entry the hit
+//! count H; stats (may be null): 3 zeroed counters, see profiles.hip ProfileHitArgs. Write pass: keys and pidx (H each)
+void profileHits(bool write, int64_t C, int64_t ns, int64_t nItems, int64_t H, const double* cxyz, const Box& box,
+                 const FofGrid& g, const ProfileTables& t, int seg, const FofBuffers& B, const PairSorted& S,
+                 const ProfileBuffers& P, int64_t* itemHits, uint64_t* keys, int32_t* pidx, unsigned long long* stats,
+                 hipStream_t s);
+//! bound on the (centre, segment) pairs of H sorted hits: the rows of the reduction's work arrays
+int64_t profileMaxSegments(int64_t C, int64_t H, int seg);
+//! starts, partial sums, combination and the crossing search on the sorted hits (H >= 1); rho: T thresholds
+void profileReduce(int64_t C, int64_t H, int64_t np, int64_t ns, const Box& box, const ProfileTables& t, int T,
+                   const double* rho, int seg, const uint64_t* keysSorted, const int32_t* hperm, const int32_t* pidx,
+                   const int32_t* perm, const PairSorted& S, const ProfileFields& f, const double* cxyz,
+                   const double* vc, const ProfileWork& W, const ProfileOut& O, void* tmp, size_t tmpBytes,
+                   hipStream_t s);
+unsigned dcheckProfiles();
 void computeGravityLists(int64_t first, int64_t last, const int32_t* child, const int32_t* n2l, const int32_t* ns,
                          const int32_t* ne, const double* centers, const void* mp, const double* x, const double* y,
                          const double* z, unsigned long long* stats, void* scratch, int testFrontCap, int capM,

@@ -25,6 +25,11 @@ Commands:
       [--bound [--eps E] [--G g] [--max-iter K] [--thermal] [--bound-mask FILE.npy]]
                                               unbinds the groups (ops/groups.py; eps defaults to 0.1 linking lengths) and
                                               adds: bound_count bound_mass bvx bvy bvz ekin eint epot px py pz most_bound
+      [--so 200[,500] --so-rmax R [--profile-bins B --profile-rmin r] [--profiles-out FILE]]
+                                              spherical-overdensity radii and masses against the box mean density
+                                              (ops/profiles.py) about the bound centre (with --bound) or the centre of
+                                              mass; adds per overdensity: R M N truncated; the profiles go to FILE as
+                                              group r_lo r_hi count mass density vr sigma_r sigma
   pairs FILE [-s STEP] --rmin A --rmax B --bins N [--log] [--velocity] [--mass] [--stride K] [--device cuda]
       [-o pairs.txt]                          pair counts per radial bin (ops/pairstats.py): r_lo r_hi count [ww]
                                               [S2L S2T S3L] [xi]
@@ -353,6 +358,38 @@ def cmd_fof(args):
         head += f" bound_count bound_mass bvx bvy bvz ekin eint epot px py pz most_bound  ({bc['iterations']} iterations)"
         if args.bound_mask:
             np.save(args.bound_mask, mask.cpu().numpy())
+    if args.so:
+        from ..ops.profiles import profile_quantities, radial_profiles
+
+        if args.so_rmax is None:
+            raise SystemExit("fof: --so needs --so-rmax, the radius out to which the spheres are searched")
+        deltas = [float(v) for v in args.so.split(",")]
+        rmin = 0.01 * args.so_rmax if args.profile_rmin is None else args.profile_rmin
+        edges = np.geomspace(rmin, args.so_rmax, args.profile_bins + 1) if args.profile_bins else \
+            np.array([0.0, args.so_rmax])
+        nan_to = lambda a, b: torch.where(torch.isnan(a), b, a)
+        cen, vc = (nan_to(bc["centre"], cat["com"]), nan_to(bc["vel"], cat["vel"])) if args.bound else \
+            (cat["com"], cat["vel"])
+        rho_ref = float(t["m"].sum()) / (lx * ly * lz)
+        prof = radial_profiles(cen.contiguous(), t["x"], t["y"], t["z"], t["m"], box, edges,
+                               v=(t["vx"], t["vy"], t["vz"]), vc=vc.contiguous(),
+                               thresholds=[v * rho_ref for v in deltas])
+        for k, delta in enumerate(deltas):
+            cols += [prof["so_radius"][:, k], prof["so_mass"][:, k], prof["so_count"][:, k].double(),
+                     prof["so_truncated"][:, k].double()]
+            fmt += ["%.17e", "%.17e", "%d", "%d"]
+            head += " R_{0:g} M_{0:g} N_{0:g} truncated_{0:g}".format(delta)
+        head += f"  (reference density {rho_ref:.17e}, r_max {args.so_rmax:.17e})"
+        if args.profiles_out:
+            q = profile_quantities(prof, edges)
+            ng, nbins = prof["count"].shape
+            e = torch.as_tensor(edges)
+            pcols = [torch.arange(ng).repeat_interleave(nbins).double(), e[:-1].repeat(ng), e[1:].repeat(ng),
+                     prof["count"].double().flatten(), prof["mass"].flatten(), q["density"].flatten(),
+                     q["vr"].flatten(), q["sigma_r"].flatten(), q["sigma"].flatten()]
+            np.savetxt(args.profiles_out, torch.stack([c.cpu() for c in pcols], dim=1).numpy(),
+                       fmt=["%d", "%.17e", "%.17e", "%d"] + ["%.17e"] * 5,
+                       header="group r_lo r_hi count mass density vr sigma_r sigma")
     table = torch.stack([c.cpu() for c in cols], dim=1).numpy() if cat["label"].numel() else np.zeros((0, len(fmt)))
     out = args.out or "groups.txt"
     np.savetxt(out, table, fmt=fmt, header=f"{head}  (linking length {ll:.17e}, min members {args.min_members})")
@@ -482,6 +519,11 @@ def main(argv=None):
     p.add_argument("--max-iter", type=int, default=20)
     p.add_argument("--thermal", action="store_true")
     p.add_argument("--bound-mask", default=None)
+    p.add_argument("--so", default=None)
+    p.add_argument("--so-rmax", type=float, default=None)
+    p.add_argument("--profile-bins", type=int, default=0)
+    p.add_argument("--profile-rmin", type=float, default=None)
+    p.add_argument("--profiles-out", default=None)
     p = sub.add_parser("pairs")
     p.add_argument("file")
     p.add_argument("-s", "--step", type=int, default=None)
