@@ -329,7 +329,9 @@ __device__ __forceinline__ bool searchGroup(int64_t g, int64_t first, int64_t la
                 }
             }
             // 1. search box of the pass
-            double r     = 2.0 * double(hi);
+            // (the pair test's radius^2 is the fp32 product 4 h h, which can round up: its root exceeds 2 h by up to
+            // 2^-25 of it, and a neighbor in that shell on the edge of its leaf's box lay outside a box of x +- 2h)
+            double r     = (2.0 + 2.4e-7) * double(hi);
             double lo[3] = {act ? xi - r : 1e300, act ? yi - r : 1e300, act ? zi - r : 1e300};
             double hh[3] = {act ? xi + r : -1e300, act ? yi + r : -1e300, act ? zi + r : -1e300};
             double gc[3], gs[3];
@@ -478,7 +480,6 @@ __device__ __forceinline__ bool searchGroup(int64_t g, int64_t first, int64_t la
             // 3. touched leaves, compacted in place; chunk count -> rows of the chunk table
             {
                 const float rt  = 2.0f * hi + 4.0f * delta;
-                const float rt2 = act ? rt * rt : -1.0f;
                 unsigned nch    = 0;
                 nT              = 0;
 #ifdef SPHX_NS_TIMING_NOTOUCH // timing experiments only (no usable lists)
@@ -495,10 +496,18 @@ __device__ __forceinline__ bool searchGroup(int64_t g, int64_t first, int64_t la
                     if (relOk)
                     {
                         // leaf box in the group frame (uniform), point-box distance per lane in fp32
-                        const float ax = fmaxf(fabsf(xir - float(fold(lc[0] - gc[0], 0))) - float(lh[0]), 0.0f);
-                        const float ay = fmaxf(fabsf(yir - float(fold(lc[1] - gc[1], 1))) - float(lh[1]), 0.0f);
-                        const float az = fmaxf(fabsf(zir - float(fold(lc[2] - gc[2], 2))) - float(lh[2]), 0.0f);
-                        touch = ax * ax + ay * ay + az * az < rt2;
+                        const float dcx = float(fold(lc[0] - gc[0], 0)), dcy = float(fold(lc[1] - gc[1], 1)),
+                                    dcz = float(fold(lc[2] - gc[2], 2));
+                        const float lhx = float(lh[0]), lhy = float(lh[1]), lhz = float(lh[2]);
+                        const float ax  = fmaxf(fabsf(xir - dcx) - lhx, 0.0f);
+                        const float ay  = fmaxf(fabsf(yir - dcy) - lhy, 0.0f);
+                        const float az  = fmaxf(fabsf(zir - dcz) - lhz, 0.0f);
+                        // the box is rounded to fp32 at the leaf's own scale: the center offset, the difference to it
+                        // and the half size carry 2^-24 of their magnitudes each, <= 1.2e-7 (|dc| + lh) summed over
+                        // the dimensions (taken twice here). delta covers the group's scale only, and a sparse leaf
+                        // can be 10^4 times larger than the neighborhood of a dense group that reaches its edge
+                        const float rl = rt + 2.4e-7f * (fabsf(dcx) + fabsf(dcy) + fabsf(dcz) + lhx + lhy + lhz);
+                        touch = act && ax * ax + ay * ay + az * az < rl * rl;
                     }
                     else { touch = act && pointBoxDistSq(ip, lc, lh, box) < radiusSq; }
                     if (!ballot(touch)) continue;
