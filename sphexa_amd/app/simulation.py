@@ -14,6 +14,7 @@ The global bucket size follows the reference: max(bucketSizeFocus, N / (100 * nu
 
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -121,23 +122,66 @@ class Simulation:
                     nsum=d.totalNeighbors)
 
     def image(self, field: str, kind: str = "slice", axis: str = "z", res=(512, 512), window=None, s0=None, s1=None,
-              weighted: str | None = "default", h_floor: float = 0.5) -> torch.Tensor:
-        """(nv, nu) float32 image of a particle field over all ranks (ops/image.py): a kernel-weighted slice at ``s0``
-        or a column projection over [s0, s1]. ``"rho"`` is the SPH density sum_j m_j W (slice) or the column density
-        sum_j m_j F (projection). Other fields are ``weighted`` by "volume" (sum V A W / sum V W, the default of a
-        slice), by "mass" (sum m A F / sum m F, the default of a projection) or not at all (None: sum V A W, the
-        unnormalised interpolant); pixels that no particle reaches are 0."""
+              weighted: str | None = "default", h_floor: float = 0.5, kappa: float | None = None) -> torch.Tensor:
+        """float32 image of a particle field (ops/image.py): (nv, nu) over all ranks for a kernel-weighted slice at
+        ``s0`` or a column projection over [s0, s1], the (2, nv, nu) stack [I, T] for an opacity rendering of [s0, s1].
+        ``"rho"`` is the SPH density sum_j m_j W (slice) or the column density sum_j m_j F (projection). Other fields
+        are ``weighted`` by "volume" (sum V A W / sum V W, the default of a slice), by "mass" (sum m A F / sum m F, the
+        default of a projection) or not at all (None: sum V A W, the unnormalised interpolant); pixels that no particle
+        reaches are 0.
+        ``kind="render"``: the field is the emission of particles of opacity ``kappa`` (per mass), composited front
+        to back along ``axis`` ("-x", "-y", "-z": from the far side); it takes no weighting. ``kappa`` defaults to
+        window area / mass of the slab's particles inside the window, a mean optical depth of 1. One rank only: the
+        result depends on the order along the line of sight across the ranks' domains."""
         from ..ops.image import sph_image
 
         d, first, last = self.d, self.domain.start_index(), self.domain.end_index()
-        w = self._field_weights("image", [field], weighted, "volume" if kind == "slice" else "mass")
+        if kind == "render":
+            w = self._render_weights(field, axis, window, s0, s1, weighted, kappa)
+        elif kappa is not None:
+            raise ValueError("image: kappa belongs to kind='render'")
+        else:
+            w = self._field_weights("image", [field], weighted, "volume" if kind == "slice" else "mass")
         img = sph_image(d["x"], d["y"], d["z"], d["h"], torch.stack(w).to(torch.float32), self.domain.box, kind=kind,
                         axis=axis, window=window, res=res, s0=s0, s1=s1, h_floor=h_floor, first=first, last=last,
                         sinc_index=d.sincIndex)
+        if kind == "render":
+            return img
         img = self.comm.allreduce(img)
         if len(w) == 1:
             return img[0]
         return torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))
+
+    def _render_weights(self, field, axis, window, s0, s1, weighted, kappa):
+        """the two channels of an opacity rendering: [kappa m, field]"""
+        if weighted != "default":
+            raise ValueError("image: a rendering takes no weighting (channel 0 is kappa m, channel 1 the field)")
+        if self.comm.size > 1:
+            raise NotImplementedError("image: renderings are not composited across ranks yet (the domains are not "
+                                      "ordered in depth); run on one rank or render a gathered snapshot "
+                                      "(python -m sphexa_amd.tools image --kind render)")
+        d, box, own = self.d, self.domain.box, slice(self.domain.start_index(), self.domain.end_index())
+        if kappa is None:
+            a = "xyz".index(axis[-1])
+            iu, iv = (a + 1) % 3, (a + 2) % 3
+            lo, hi = list(box.lo), list(box.hi)
+            if window is not None:
+                lo[iu], hi[iu], lo[iv], hi[iv] = (float(t) for t in window)
+            lo[a], hi[a] = (-math.inf if s0 is None else float(s0)), (math.inf if s1 is None else float(s1))
+            inside = torch.ones_like(d["m"][own], dtype=torch.bool)
+            for k, c in enumerate("xyz"):
+                inside &= (d[c][own] >= lo[k]) & (d[c][own] <= hi[k])
+            mass = float((d["m"][own].double() * inside).sum())
+            if not mass > 0:
+                raise ValueError("image: no mass inside the window's slab; give kappa")
+            kappa = (hi[iu] - lo[iu]) * (hi[iv] - lo[iv]) / mass
+        if field == "rho" and not d.is_allocated("rho"):  # VE runs hold (xm, kx) instead: rho = kx m / xm
+            if not (d.is_allocated("xm") and d.is_allocated("kx")):
+                raise ValueError("image: this run holds neither rho nor the VE fields xm and kx")
+            source = d["kx"] * d["m"] / d["xm"]
+        else:
+            source = d[field]
+        return [float(kappa) * d["m"].to(torch.float32), source.to(torch.float32)]
 
     def _field_weights(self, what, fields, weighted, default):
         """per-particle channel weights of image, volume and power_spectrum: [m] for ``rho`` (the kernel sum of the

@@ -1,7 +1,8 @@
-// SPH slices and column projections on the host: the definition of ops/image.py summed in fp64, OpenMP over image
-// rows. Every row visits every particle (short, not fast); the gfx950 path is hip/image.hip.
+// SPH slices, column projections and opacity renderings on the host: the definitions of ops/image.py in fp64, OpenMP
+// over image rows. Every row visits every particle (short, not fast); the gfx950 path is hip/image.hip.
 #include <algorithm>
 #include <cmath>
+#include <numeric>
 #include <vector>
 
 #include "cpu_api.hpp"
@@ -20,6 +21,20 @@ void sphImage(int64_t first, int64_t last, int64_t n, const double* x, const dou
     const double* pos[3] = {x, y, z};
     const double halfPi  = 1.5707963267948966;
     const int su0 = V.perU ? -1 : 0, sv0 = V.perV ? -1 : 0;
+    // rendering: the particles of the slab in compositing order, a stable sort by the depth key (ties by index);
+    // every row then walks them in that order, shift codes ascending (sv outer, su inner)
+    std::vector<int64_t> order;
+    if (V.render)
+    {
+        if (C != 2) throw std::invalid_argument("sphImage: a rendering has two channels");
+        order.resize(size_t(last - first));
+        std::iota(order.begin(), order.end(), first);
+        std::vector<uint64_t> key(order.size());
+        for (size_t k = 0; k < key.size(); ++k)
+            key[k] = imageDepthKey(V, pos[V.ia][first + int64_t(k)]);
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int64_t a, int64_t b) { return key[size_t(a - first)] < key[size_t(b - first)]; });
+    }
 #pragma omp parallel for schedule(dynamic, 4)
     for (int py = 0; py < V.nv; ++py)
     {
@@ -27,8 +42,10 @@ void sphImage(int64_t first, int64_t last, int64_t n, const double* x, const dou
         // separations scaled by pixel / h
         const double gy = py + 0.5;
         std::vector<double> row(size_t(C) * V.nu, 0.0);
-        for (int64_t j = first; j < last; ++j)
+        if (V.render) std::fill(row.begin() + V.nu, row.end(), 1.0); // (I, T) = (0, 1)
+        for (int64_t t = first; t < last; ++t)
         {
+            const int64_t j = V.render ? order[size_t(t - first)] : t;
             const double hj = std::max(double(h[j]), V.hMin);
             double dz, R;
             if (!imageDepth(V, pos[V.ia][j], hj, dz, R)) continue;
@@ -60,6 +77,14 @@ void sphImage(int64_t first, int64_t last, int64_t n, const double* x, const dou
                         {
                             const double a = halfPi * std::sqrt(q2);
                             val            = V.K * std::pow(a > 0 ? std::sin(a) / a : 1.0, V.n) * (ih * ih * ih);
+                        }
+                        if (V.render)
+                        {
+                            const double tau = double(w[j]) * val;
+                            double &I = row[k], &T = row[size_t(V.nu) + k];
+                            I += T * -std::expm1(-tau) * double(w[size_t(n) + j]);
+                            T *= std::exp(-tau);
+                            continue;
                         }
                         for (int c = 0; c < C; ++c)
                             row[size_t(c) * V.nu + k] += double(w[size_t(c) * n + j]) * val;

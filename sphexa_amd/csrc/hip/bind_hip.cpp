@@ -635,12 +635,20 @@ PYBIND11_MODULE(_sphx_hip, m)
     m.def("device_checks_enabled", &deviceChecksEnabled);
     // ------------------------------------------------------------------------------------------------- images
     using ViewArr = std::array<double, 11>;
+    m.def("image_depth_keys",
+          [](int64_t first, int64_t last, Ptr x, Ptr y, Ptr z, const BoxArr& box, const ViewArr& view, int nu, int nv,
+             Ptr keys, Ptr s)
+          {
+              imageDepthKeys(first, last, P<double>(x), P<double>(y), P<double>(z),
+                             makeImageView(toBox(box), view.data(), nu, nv), P<uint64_t>(keys), St(s));
+          });
     m.def("image_records",
-          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, const BoxArr& box,
-             const ViewArr& view, int nu, int nv, Ptr rec, Ptr counts, Ptr s)
+          [](int64_t first, int64_t last, int64_t n, Ptr x, Ptr y, Ptr z, Ptr h, Ptr w, int C, Ptr perm,
+             const BoxArr& box, const ViewArr& view, int nu, int nv, Ptr rec, Ptr counts, Ptr s)
           {
               imageRecords(first, last, n, P<double>(x), P<double>(y), P<double>(z), P<float>(h), P<float>(w), C,
-                           makeImageView(toBox(box), view.data(), nu, nv), P<ImageRec>(rec), P<int64_t>(counts), St(s));
+                           P<int32_t>(perm), makeImageView(toBox(box), view.data(), nu, nv), P<ImageRec>(rec),
+                           P<int64_t>(counts), St(s));
           });
     m.def("image_fill",
           [](int64_t np, const BoxArr& box, const ViewArr& view, int nu, int nv, Ptr rec, Ptr offsets, Ptr keys, Ptr s)
@@ -660,6 +668,15 @@ PYBIND11_MODULE(_sphx_hip, m)
               imageTiles(C, np, total, P<uint64_t>(keys), P<ImageRec>(rec), V, ntiles, segment, nblocks,
                          P<int64_t>(start), P<int64_t>(segOff), P<float>(table), tableLen, P<float>(work),
                          P<float>(img), St(s));
+          });
+    m.def("image_render",
+          [](int64_t np, int64_t total, Ptr keys, Ptr rec, const BoxArr& box, const ViewArr& view, int nu, int nv,
+             int ntiles, int64_t segment, int64_t nblocks, Ptr start, Ptr segOff, Ptr table, int tableLen, Ptr work,
+             Ptr img, Ptr s)
+          {
+              imageRender(np, total, P<uint64_t>(keys), P<ImageRec>(rec), makeImageView(toBox(box), view.data(), nu, nv),
+                          ntiles, segment, nblocks, P<int64_t>(start), P<int64_t>(segOff), P<float>(table), tableLen,
+                          P<float>(work), P<float>(img), St(s));
           });
 
     // ------------------------------------------------------------------------------------- friends-of-friends

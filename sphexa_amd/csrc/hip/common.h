@@ -34,7 +34,8 @@
  *        re-test source index out of range, 6 image block's tile index out of range, 7 image entry's record index
  *        out of range, 8 volume block's brick index out of range, 9 volume entry's record index out of range,
  *        10 pair statistics: a sorted range index out of range, 11 bound groups: a member, group or item index out
- *        of range, 12 profiles: a slot, item, hit, particle or segment index out of range */
+ *        of range, 12 profiles: a slot, item, hit, particle or segment index out of range, 13 image rendering: a depth
+ *        permutation index out of range */
 #ifdef SPHX_DEVICE_CHECKS
 namespace sphx::hip
 {

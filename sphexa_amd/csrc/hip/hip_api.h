@@ -342,10 +342,13 @@ unsigned dcheckGravity();
 unsigned dcheckImage();
 
 // image.hip: SPH slices and column projections (ops/image.py holds the sequence: records + counts, scan, fill, sort,
-// ranges, scan, tiles)
+// ranges, scan, tiles) and opacity renderings (depth keys + sort first; records in that order via perm, null for the
+// other kinds; imageRender in place of imageTiles)
+void imageDepthKeys(int64_t first, int64_t last, const double* x, const double* y, const double* z,
+                    const ImageView& V, uint64_t* keys, hipStream_t s);
 void imageRecords(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
-                  const float* h, const float* w, int C, const ImageView& V, ImageRec* rec, int64_t* counts,
-                  hipStream_t s);
+                  const float* h, const float* w, int C, const int32_t* perm, const ImageView& V, ImageRec* rec,
+                  int64_t* counts, hipStream_t s);
 void imageFill(int64_t np, const ImageView& V, const ImageRec* rec, const int64_t* offsets, uint64_t* keys,
                hipStream_t s);
 void imageRanges(int64_t total, const uint64_t* keys, int ntiles, int64_t segment, int64_t* start, int64_t* nseg,
@@ -353,6 +356,9 @@ void imageRanges(int64_t total, const uint64_t* keys, int ntiles, int64_t segmen
 void imageTiles(int C, int64_t np, int64_t total, const uint64_t* keys, const ImageRec* rec, const ImageView& V,
                 int ntiles, int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff,
                 const float* table, int tableLen, float* work, float* img, hipStream_t s);
+void imageRender(int64_t np, int64_t total, const uint64_t* keys, const ImageRec* rec, const ImageView& V, int ntiles,
+                 int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff, const float* table,
+                 int tableLen, float* work, float* img, hipStream_t s);
 
 // volume.hip: SPH volumes on 3-D grids, binned to 8^3-voxel bricks (ops/volume.py holds the sequence: records +
 // counts, scan, fill, sort, ranges, scan, bricks), and the shell binning of a half spectrum (ops/spectrum.py)

@@ -1,5 +1,5 @@
-/*! SPH slices and column projections as images on gfx950: particles are binned to 32x32-pixel tiles, every tile sums
- *  its own sorted list (definitions: ops/image.py; host form: cpu/image_cpu.cpp).
+/*! SPH slices, column projections and opacity renderings as images on gfx950: particles are binned to 32x32-pixel
+ *  tiles, every tile sums (composites) its own sorted list (definitions: ops/image.py; host form: cpu/image_cpu.cpp).
  *
  *  1. imageRecordsKernel, one thread per particle: the pixel-space centre, 1/h_eff and (slices) the depth offset over h
  *     are formed in fp64 from the coordinates and rounded once to fp32 into a 32-B record next to the weights and the
@@ -22,6 +22,17 @@
  *     interpolates the F_n table in u = q^2/4, copied into LDS once per block (h^-2 folded into the weights).
  *  5. A tile of one segment stores its pixels to the image; the segments of a longer list store partial tiles to a
  *     workspace and imageSumKernel adds them in segment order (deterministic as well).
+ *  6. Opacity renderings composite a pixel's entries front to back, so the list order is part of the result.
+ *     imageDepthKeysKernel writes the order-preserving uint64 image of every particle's fp64 depth, the stable sample
+ *     sort turns the keys into a permutation (ties by particle index) and imageRecordsKernel forms record k from
+ *     particle perm[k]: the entry keys of step 2 then sort into depth order inside every tile with no further work.
+ *     imageRenderKernel walks the list as step 4 does (same staging, walkEntries) and carries (I, T) per pixel:
+ *     tau = kappa m h^-2 F_n, a = exp(-tau), I += T (1 - a) s, T *= a. A lane's four pixels are four independent
+ *     chains; per entry a chain is one multiply-add (I) and one multiply (T), everything else (table read,
+ *     v_exp_f32, 1 - a) is computed off the chains. Segments start from (0, 1) and store (I_s, T_s) partial tiles;
+ *     imageComposeKernel folds them in list order, I += T I_s, T *= T_s.
+ *     Open lead: no early-out on opaque pixels. A segment does not know the transmittance in front of it, but a block
+ *     could stop staging batches once all of its own 1024 T are 0 (one __syncthreads_and per batch).
  *
  *  No matrix instructions: the distances are 2-D/3-D (an MFMA form of |p - c|^2 would have K = 3 or 4 and spend the
  *  tile on padding), and the cost is the culling and the transcendental / table read per pixel, not the dot product.
@@ -108,18 +119,34 @@ __device__ __forceinline__ void forEachTile(const ImageRec& r, const ImageGeom& 
         }
 }
 
+//! rendering: the depth key of every particle of [first, first + np), a = its view-axis coordinates
+__global__ void __launch_bounds__(256)
+imageDepthKeysKernel(int64_t first, int64_t np, const double* __restrict__ a, ImageView V, uint64_t* __restrict__ keys)
+{
+    const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (k < np) keys[k] = imageDepthKey(V, a[first + k]);
+}
+
+//! record k of particle first + perm[k] (a rendering's depth order) or, without a permutation, first + k
 __global__ void __launch_bounds__(256)
 imageRecordsKernel(int64_t first, int64_t last, int64_t n, const double* __restrict__ x, const double* __restrict__ y,
                    const double* __restrict__ z, const float* __restrict__ h, const float* __restrict__ w, int C,
-                   ImageView V, ImageGeom g, ImageRec* __restrict__ rec, int64_t* __restrict__ counts)
+                   const int32_t* __restrict__ perm, ImageView V, ImageGeom g, ImageRec* __restrict__ rec,
+                   int64_t* __restrict__ counts)
 {
     const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int64_t i = first + k;
-    if (i > last) return;
-    if (i == last)
+    if (first + k > last) return;
+    if (first + k == last)
     {
         counts[k] = 0; // the scan's last element: its result is the total
         return;
+    }
+    int64_t i = first + k;
+    if (perm)
+    {
+        const int64_t pk = perm[k];
+        SPHX_DCHECK(pk >= 0 && pk < last - first, 13);
+        if (pk >= 0 && pk < last - first) i = first + pk;
     }
     const double p[3] = {x[i], y[i], z[i]};
     const double hj   = sphx::smax(double(h[i]), V.hMin);
@@ -245,16 +272,28 @@ __device__ __forceinline__ void quadOrigin(int t, int& px, int& py)
     py = wave * 8 + 2 * (lane >> 4);
 }
 
-template<class Profile, int C>
-__global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profile prof)
+//! LDS of a tile block's walk: one batch of 256 entries, SoA, with NW staged weights, and every wave's survivors.
+//! Depth: the entries carry a depth term z2 = (dz / h)^2 (slices); without it nothing is staged or added for it
+template<int NW, bool Depth>
+struct TileStage
 {
-    __shared__ float sTab[Profile::kLds];
-    __shared__ float sCu[kTileBlock], sCv[kTileBlock], sAu[kTileBlock], sAv[kTileBlock], sZ2[kTileBlock],
-        sRu[kTileBlock], sRv[kTileBlock], sW[C][kTileBlock];
-    __shared__ uint16_t sList[kTileBlock / kWave][kTileBlock];
+    float cu[kTileBlock], cv[kTileBlock], au[kTileBlock], av[kTileBlock], z2[Depth ? kTileBlock : 1], ru[kTileBlock],
+        rv[kTileBlock], w[NW][kTileBlock];
+    uint16_t list[kTileBlock / kWave][kTileBlock];
+};
 
+//! the (tile, segment) of a block: its tile, the tile's segment count, its entries [e0, e1) and the thread's quad
+struct TileBlock
+{
+    int tu, tv, qx, qy;
+    int64_t nseg, e0, e1;
+};
+
+//! @return false for the blocks past the scanned block count (the grid is the host's upper bound)
+__device__ __forceinline__ bool tileBlockOf(const TileArgs& A, TileBlock& B)
+{
     const int64_t b = blockIdx.x;
-    if (b >= A.segOff[A.ntiles]) return; // (the grid is the host's upper bound of the block count)
+    if (b >= A.segOff[A.ntiles]) return false;
     // tile of this block: the last t with segOff[t] <= b
     int tile;
     {
@@ -268,31 +307,36 @@ __global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profil
         tile = lo;
     }
     SPHX_DCHECK(tile >= 0 && tile < A.ntiles && A.segOff[tile] <= b && b < A.segOff[tile + 1], 6);
-    const int64_t seg0  = A.segOff[tile];
-    const int64_t nseg  = A.segOff[tile + 1] - seg0;
-    const int64_t tEnd  = A.start[tile + 1];
-    const int64_t e0    = sphx::smin(A.start[tile] + (b - seg0) * A.segment, tEnd);
-    const int64_t e1    = sphx::smin(e0 + A.segment, tEnd);
-    const int nBatch    = int((e1 - e0 + kTileBlock - 1) / kTileBlock);
-    const int tid       = threadIdx.x;
-    const int wave      = tid >> 6;
-    const int tu = tile % A.g.ntu, tv = tile / A.g.ntu;
-    int qx, qy;
-    quadOrigin(tid, qx, qy);
+    const int64_t seg0 = A.segOff[tile];
+    const int64_t tEnd = A.start[tile + 1];
+    B.nseg             = A.segOff[tile + 1] - seg0;
+    B.e0               = sphx::smin(A.start[tile] + (b - seg0) * A.segment, tEnd);
+    B.e1               = sphx::smin(B.e0 + A.segment, tEnd);
+    B.tu               = tile % A.g.ntu;
+    B.tv               = tile / A.g.ntu;
+    quadOrigin(threadIdx.x, B.qx, B.qy);
+    return true;
+}
+
+/*! @brief walks the block's entries in list order, shared by the summing and the compositing tile kernel: stages them
+ *         in batches of 256 (fold(record, w) fills an entry's staged weights and returns its depth term, used only
+ *         with Depth), culls every batch against the wave's strip and calls body(q2, w) for every survivor, with q^2
+ *         at the quad's four pixels. The ballot compaction keeps the survivors in entry order (a lane's slot is the
+ *         count of the hits before it): the sums are thereby reproducible, and the compositing kernel's result
+ *         depends on it. */
+template<int NW, bool Depth, class Fold, class Body>
+__device__ __forceinline__ void walkEntries(const TileArgs& A, const TileBlock& B, TileStage<NW, Depth>& st,
+                                            Fold&& fold, Body&& body)
+{
+    const int64_t e0 = B.e0, e1 = B.e1;
+    const int nBatch = int((e1 - e0 + kTileBlock - 1) / kTileBlock);
+    const int tid    = threadIdx.x;
+    const int wave   = tid >> 6;
     // pixel centres of the quad and the strip's extent of centres
-    const float fx0 = float(tu * kTile + qx) + 0.5f, fx1 = fx0 + 1.0f;
-    const float fy0 = float(tv * kTile + qy) + 0.5f, fy1 = fy0 + 1.0f;
-    const float sx0 = float(tu * kTile) + 0.5f, sx1 = sx0 + float(kTile - 1);
-    const float sy0 = float(tv * kTile + wave * 8) + 0.5f, sy1 = sy0 + 7.0f;
-
-    prof.load(sTab, A.table);
-
-    float acc[4][C];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            acc[p][c] = 0.0f;
+    const float fx0 = float(B.tu * kTile + B.qx) + 0.5f, fx1 = fx0 + 1.0f;
+    const float fy0 = float(B.tv * kTile + B.qy) + 0.5f, fy1 = fy0 + 1.0f;
+    const float sx0 = float(B.tu * kTile) + 0.5f, sx1 = sx0 + float(kTile - 1);
+    const float sy0 = float(B.tv * kTile + wave * 8) + 0.5f, sy1 = sy0 + 7.0f;
 
     const float4* rec4 = reinterpret_cast<const float4*>(A.rec);
     auto loadKey       = [&](int batch) -> uint64_t
@@ -329,16 +373,18 @@ __global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profil
             ImageRec r{r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
             float cu, cv;
             shifted(r, validCur ? su : 0, validCur ? sv : 0, A.g, cu, cv);
-            const float wgt = prof.weight(r.ih);
-            sCu[tid]    = cu;
-            sCv[tid]    = cv;
-            sAu[tid]    = A.g.au * r.ih;
-            sAv[tid]    = A.g.av * r.ih;
-            sZ2[tid]    = prof.zq2(r.zq);
-            sRu[tid]    = validCur ? r.ru : -1.0f;
-            sRv[tid]    = r.rv;
-            sW[0][tid]  = r.w0 * wgt;
-            if constexpr (C == 2) sW[1][tid] = r.w1 * wgt;
+            float w[NW];
+            const float z2 = fold(r, w);
+            if constexpr (Depth) st.z2[tid] = z2;
+            st.cu[tid] = cu;
+            st.cv[tid] = cv;
+            st.au[tid] = A.g.au * r.ih;
+            st.av[tid] = A.g.av * r.ih;
+            st.ru[tid] = validCur ? r.ru : -1.0f;
+            st.rv[tid] = r.rv;
+#pragma unroll
+            for (int c = 0; c < NW; ++c)
+                st.w[c][tid] = w[c];
         }
         __syncthreads();
 
@@ -348,11 +394,11 @@ __global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profil
         for (int r = 0; r < kTileBlock / kWave; ++r)
         {
             const int s    = r * kWave + laneId();
-            const float ru = sRu[s], rv = sRv[s], cu = sCu[s], cv = sCv[s];
+            const float ru = st.ru[s], rv = st.rv[s], cu = st.cu[s], cv = st.cv[s];
             const bool hit = ru >= 0.0f && cu - ru <= sx1 + 0.001f && cu + ru >= sx0 - 0.001f &&
                              cv - rv <= sy1 + 0.001f && cv + rv >= sy0 - 0.001f;
             const uint64_t m = ballot(hit);
-            if (hit) sList[wave][count + popcount64(m & lanemaskLt())] = uint16_t(s);
+            if (hit) st.list[wave][count + popcount64(m & lanemaskLt())] = uint16_t(s);
             count += popcount64(m);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -361,24 +407,19 @@ __global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profil
 
         for (int k = 0; k < count; ++k)
         {
-            const int s    = sList[wave][k];
-            const float cu = sCu[s], cv = sCv[s], au = sAu[s], av = sAv[s], z2 = sZ2[s];
-            float w[C];
-            w[0] = sW[0][s];
-            if constexpr (C == 2) w[1] = sW[1][s];
+            const int s    = st.list[wave][k];
+            const float cu = st.cu[s], cv = st.cv[s], au = st.au[s], av = st.av[s];
+            float w[NW];
+#pragma unroll
+            for (int c = 0; c < NW; ++c)
+                w[c] = st.w[c][s];
             const float a0 = (fx0 - cu) * au, a1 = (fx1 - cu) * au;
             const float b0 = (fy0 - cv) * av, b1 = (fy1 - cv) * av;
-            const float a02 = a0 * a0 + z2, a12 = a1 * a1 + z2, b02 = b0 * b0, b12 = b1 * b1;
+            const float z2  = Depth ? st.z2[s] : 0.0f; // (not read, not added without Depth)
+            const float a02 = Depth ? a0 * a0 + z2 : a0 * a0, a12 = Depth ? a1 * a1 + z2 : a1 * a1;
+            const float b02 = b0 * b0, b12 = b1 * b1;
             const float q2[4] = {a02 + b02, a12 + b02, a02 + b12, a12 + b12};
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-                if (q2[p] < 4.0f)
-                {
-                    const float f = prof(sTab, q2[p]);
-#pragma unroll
-                    for (int c = 0; c < C; ++c)
-                        acc[p][c] += w[c] * f;
-                }
+            body(q2, w);
         }
 
         keyCur   = keyNext;
@@ -387,29 +428,128 @@ __global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profil
         r0       = n0;
         r1       = n1;
     }
+}
 
-    // pixel p of the quad: (qx + (p & 1), qy + (p >> 1))
-    if (nseg == 1)
+/*! @brief the quad's values val[c][p], pixel p = (qx + (p & 1), qy + (p >> 1)): to the image if the tile has one
+ *         segment, else to the block's partial tile in the workspace (thread-major) */
+template<int C>
+__device__ __forceinline__ void storeQuad(const TileArgs& A, const TileBlock& B, const float (&val)[C][4])
+{
+    if (B.nseg == 1)
     {
 #pragma unroll
         for (int p = 0; p < 4; ++p)
         {
-            const int px = tu * kTile + qx + (p & 1), py = tv * kTile + qy + (p >> 1);
+            const int px = B.tu * kTile + B.qx + (p & 1), py = B.tv * kTile + B.qy + (p >> 1);
             if (px < A.g.nu && py < A.g.nv)
 #pragma unroll
                 for (int c = 0; c < C; ++c)
-                    A.img[(size_t(c) * A.g.nv + py) * A.g.nu + px] = acc[p][c];
+                    A.img[(size_t(c) * A.g.nv + py) * A.g.nu + px] = val[c][p];
         }
     }
     else
     {
-        float* out = A.work + size_t(b) * C * (kTile * kTile);
+        float* out = A.work + size_t(blockIdx.x) * C * (kTile * kTile);
 #pragma unroll
         for (int c = 0; c < C; ++c)
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                out[(c * 4 + p) * kTileBlock + tid] = acc[p][c];
+                out[(c * 4 + p) * kTileBlock + threadIdx.x] = val[c][p];
     }
+}
+
+template<class Profile, int C>
+__global__ void __launch_bounds__(kTileBlock) imageTileKernel(TileArgs A, Profile prof)
+{
+    __shared__ float sTab[Profile::kLds];
+    // (projections stage their zero depth term as slices do: without it the compiler pairs the multiply-adds of q^2
+    // differently and the last bits of the existing kinds change)
+    __shared__ TileStage<C, true> st;
+    TileBlock B;
+    if (!tileBlockOf(A, B)) return;
+    prof.load(sTab, A.table); // (in LDS by the walk's first barrier)
+
+    float acc[C][4];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            acc[c][p] = 0.0f;
+
+    walkEntries(
+        A, B, st,
+        [&](const ImageRec& r, float(&w)[C])
+        {
+            const float wgt = prof.weight(r.ih);
+            w[0]            = r.w0 * wgt;
+            if constexpr (C == 2) w[1] = r.w1 * wgt;
+            return prof.zq2(r.zq);
+        },
+        [&](const float(&q2)[4], const float(&w)[C])
+        {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (q2[p] < 4.0f)
+                {
+                    const float f = prof(sTab, q2[p]);
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        acc[c][p] += w[c] * f;
+                }
+        });
+    storeQuad<C>(A, B, acc);
+}
+
+constexpr float kLog2e     = 1.44269504088896340736f;
+constexpr float kSmallTau = 0.25f; // below: 1 - exp(-tau) by its series (renderStep)
+
+/*! @brief one compositing step of a pixel: I += T (1 - a) s, T *= a with a = exp(-tau) as the hardware's exp2
+ *         (v_exp_f32) of -tau log2 e. Only the last two operations are on the pixel's dependent chains.
+ *         1 - a: the subtraction itself is exact for a >= 1/2, so its error is that of a, about an ulp of a (6e-8),
+ *         and relative to 1 - a ~ tau that grows as 1 / tau. Below |tau| = 1/4 (relative error of the subtraction:
+ *         up to 5e-7) the alternating series tau (1 - tau/2 + tau^2/6 - ... - tau^5/720) is used instead; its first
+ *         dropped term, tau^6/5040 < 4.9e-8, is below half an ulp of the bracket. */
+__device__ __forceinline__ void renderStep(float tau, float s, float& I, float& T)
+{
+    const float a = __builtin_amdgcn_exp2f(-kLog2e * tau);
+    float series  = fmaf(tau, -1.0f / 720.0f, 1.0f / 120.0f);
+    series        = fmaf(tau, series, -1.0f / 24.0f);
+    series        = fmaf(tau, series, 1.0f / 6.0f);
+    series        = fmaf(tau, series, -0.5f);
+    series        = fmaf(tau, series, 1.0f);
+    const float e = (fabsf(tau) < kSmallTau ? tau * series : 1.0f - a) * s;
+    I             = fmaf(T, e, I);
+    T *= a;
+}
+
+/*! @brief opacity rendering of a (tile, segment): the block shape, staging and culling of imageTileKernel, the entries
+ *         (in depth order, see imageRecordsKernel) composited from (I, T) = (0, 1). Staged weights: kappa m h^-2 and
+ *         the source value. Output channels: 0 = I, 1 = T. */
+__global__ void __launch_bounds__(kTileBlock) imageRenderKernel(TileArgs A)
+{
+    __shared__ float sTab[ProjProfile::kLds];
+    __shared__ TileStage<2, false> st;
+    TileBlock B;
+    if (!tileBlockOf(A, B)) return;
+    const ProjProfile prof;
+    prof.load(sTab, A.table); // (in LDS by the walk's first barrier)
+
+    float it[2][4] = {{0.0f, 0.0f, 0.0f, 0.0f}, {1.0f, 1.0f, 1.0f, 1.0f}};
+    walkEntries(
+        A, B, st,
+        [&](const ImageRec& r, float(&w)[2])
+        {
+            w[0] = r.w0 * prof.weight(r.ih);
+            w[1] = r.w1;
+            return 0.0f;
+        },
+        [&](const float(&q2)[4], const float(&w)[2])
+        {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (q2[p] < 4.0f) renderStep(w[0] * prof(sTab, q2[p]), w[1], it[0][p], it[1][p]);
+        });
+    storeQuad<2>(A, B, it);
 }
 
 //! tiles of several segments: their partial tiles added in segment order
@@ -445,6 +585,39 @@ __global__ void __launch_bounds__(kTileBlock) imageSumKernel(TileArgs A)
         }
 }
 
+//! a rendering's tiles of several segments: the (I_s, T_s) partial tiles composed in segment order, which is the
+//! list's depth order: (I, T) <- (I + T I_s, T T_s) from (0, 1)
+__global__ void __launch_bounds__(kTileBlock) imageComposeKernel(TileArgs A)
+{
+    const int tile     = blockIdx.x;
+    const int64_t seg0 = A.segOff[tile];
+    const int64_t nseg = A.segOff[tile + 1] - seg0;
+    if (nseg <= 1) return;
+    const int tid = threadIdx.x;
+    const int tu = tile % A.g.ntu, tv = tile / A.g.ntu;
+    int qx, qy;
+    quadOrigin(tid, qx, qy);
+    float I[4] = {0.0f, 0.0f, 0.0f, 0.0f}, T[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    for (int64_t s = 0; s < nseg; ++s)
+    {
+        const float* in = A.work + size_t(seg0 + s) * 2 * (kTile * kTile);
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+        {
+            I[p] = fmaf(T[p], in[p * kTileBlock + tid], I[p]);
+            T[p] *= in[(4 + p) * kTileBlock + tid];
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+    {
+        const int px = tu * kTile + qx + (p & 1), py = tv * kTile + qy + (p >> 1);
+        if (px >= A.g.nu || py >= A.g.nv) continue;
+        A.img[size_t(py) * A.g.nu + px]            = I[p];
+        A.img[(size_t(A.g.nv) + py) * A.g.nu + px] = T[p];
+    }
+}
+
 template<class Profile>
 void launchTiles(int C, unsigned nblocks, const TileArgs& A, const Profile& prof, hipStream_t s)
 {
@@ -458,14 +631,26 @@ void launchTiles(int C, unsigned nblocks, const TileArgs& A, const Profile& prof
 
 } // namespace
 
+void imageDepthKeys(int64_t first, int64_t last, const double* x, const double* y, const double* z,
+                    const ImageView& V, uint64_t* keys, hipStream_t s)
+{
+    if (!V.render) throw std::invalid_argument("imageDepthKeys: the view is no rendering");
+    if (last <= first) return;
+    const double* pos[3] = {x, y, z};
+    imageDepthKeysKernel<<<gridFor(last - first, 256), 256, 0, s>>>(first, last - first, pos[V.ia], V, keys);
+    SPHX_LAUNCH_CHECK();
+}
+
 void imageRecords(int64_t first, int64_t last, int64_t n, const double* x, const double* y, const double* z,
-                  const float* h, const float* w, int C, const ImageView& V, ImageRec* rec, int64_t* counts,
-                  hipStream_t s)
+                  const float* h, const float* w, int C, const int32_t* perm, const ImageView& V, ImageRec* rec,
+                  int64_t* counts, hipStream_t s)
 {
     if (C != 1 && C != 2) throw std::invalid_argument("imageRecords: one or two channels");
     if (last - first > (int64_t(1) << kPartBits)) throw std::invalid_argument("imageRecords: more than 2^30 particles");
-    imageRecordsKernel<<<gridFor(last - first + 1, 256), 256, 0, s>>>(first, last, n, x, y, z, h, w, C, V, geomOf(V),
-                                                                      rec, counts);
+    if (V.render && (C != 2 || (!perm && last > first)))
+        throw std::invalid_argument("imageRecords: a rendering has two channels and a depth order");
+    imageRecordsKernel<<<gridFor(last - first + 1, 256), 256, 0, s>>>(first, last, n, x, y, z, h, w, C, perm, V,
+                                                                      geomOf(V), rec, counts);
     SPHX_LAUNCH_CHECK();
 }
 
@@ -495,6 +680,7 @@ void imageTiles(int C, int64_t np, int64_t total, const uint64_t* keys, const Im
     if (nblocks < total / segment + ntiles || nblocks > 0x7fffffff)
         throw std::invalid_argument("imageTiles: block count");
     if (V.proj && tableLen != kImageTableLen) throw std::invalid_argument("imageTiles: F_n table length");
+    if (V.render) throw std::invalid_argument("imageTiles: a rendering is composited by imageRender");
     const TileArgs A{np, total, keys, rec, g, ntiles, segment, start, segOff, table, work, img};
     if (V.proj) launchTiles(C, unsigned(nblocks), A, ProjProfile{}, s);
     else
@@ -505,6 +691,23 @@ void imageTiles(int C, int64_t np, int64_t total, const uint64_t* keys, const Im
         p.norm = float(V.K / std::exp2(V.n * 2.651496129472318798043279295));
         launchTiles(C, unsigned(nblocks), A, p, s);
     }
+}
+
+void imageRender(int64_t np, int64_t total, const uint64_t* keys, const ImageRec* rec, const ImageView& V, int ntiles,
+                 int64_t segment, int64_t nblocks, const int64_t* start, const int64_t* segOff, const float* table,
+                 int tableLen, float* work, float* img, hipStream_t s)
+{
+    const ImageGeom g = geomOf(V);
+    if (!V.render) throw std::invalid_argument("imageRender: the view is no rendering");
+    if (ntiles != g.ntu * g.ntv) throw std::invalid_argument("imageRender: tile count");
+    if (nblocks < total / segment + ntiles || nblocks > 0x7fffffff)
+        throw std::invalid_argument("imageRender: block count");
+    if (tableLen != kImageTableLen) throw std::invalid_argument("imageRender: F_n table length");
+    const TileArgs A{np, total, keys, rec, g, ntiles, segment, start, segOff, table, work, img};
+    imageRenderKernel<<<unsigned(nblocks), kTileBlock, 0, s>>>(A);
+    SPHX_LAUNCH_CHECK();
+    imageComposeKernel<<<unsigned(ntiles), kTileBlock, 0, s>>>(A);
+    SPHX_LAUNCH_CHECK();
 }
 
 SPHX_DCHECK_READER(dcheckImage)

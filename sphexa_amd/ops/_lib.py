@@ -86,7 +86,8 @@ DEVICE_CHECK_BITS = {0: "neighbor index out of range", 1: "list blocks of a grou
                      7: "image record index out of range", 8: "volume brick index out of range",
                      9: "volume record index out of range", 10: "pair statistics sorted range index out of range",
                      11: "bound groups member, group or item index out of range",
-                     12: "profiles slot, item, hit, particle or segment index out of range"}
+                     12: "profiles slot, item, hit, particle or segment index out of range",
+                     13: "image rendering depth permutation index out of range"}
 
 
 def raise_on_device_check(where: str = ""):

@@ -14,7 +14,8 @@ Commands:
   set-parms FILE [-a] --key value ...         write settings as file attributes
   radial-profile FILE FIELD [-s STEP] [--bins B]
   slice FILE FIELD [-s STEP] [--axis z] [--width W]
-  image FILE FIELD [-s STEP] [--kind slice|projection] [--axis z] [--res 512] [--device cuda] [-o out.npy]
+  image FILE FIELD [-s STEP] [--kind slice|projection|render] [--axis z] [--kappa K] [--res 512] [--device cuda]
+        [-o out.npy]   (render: opacity rendering [I, T]; --axis=-z views from the far side)
                                               SPH-interpolated slice / column projection (ops/image.py)
   volume FILE FIELD [-s STEP] [--res 128] [--device cuda] [-o out.npy]
                                               SPH-interpolated (res, res, res) grid of FIELD (ops/volume.py)
@@ -238,19 +239,31 @@ def _step_box(args):
 
 def cmd_image(args):
     """kernel-weighted slice (volume-weighted field average, V = m / rho) or mass-weighted column projection of FIELD;
-    ``rho``: the SPH density (slice) or the column density (projection). Writes the (res, res) array as .npy"""
+    ``rho``: the SPH density (slice) or the column density (projection). Writes the (res, res) array as .npy.
+    ``--kind render``: the opacity rendering of FIELD as emission (ops/image.py), opacity ``--kappa`` per mass (default:
+    mean optical depth 1 over the box's face), front to back along ``--axis`` (-x, -y, -z: from the far side); writes the
+    (2, res, res) stack [I, T]"""
     import torch
 
     from ..ops.image import sph_image
 
     attrs, box = _step_box(args)
+    render = args.kind == "render"
+    if (args.axis.startswith("-") or args.kappa is not None) and not render:
+        raise SystemExit("a signed --axis and --kappa belong to --kind render")
     need = ["x", "y", "z", "h", "m"] + ([] if args.field == "rho" else
                                         (["vx", "vy", "vz"] if args.field == "v" else [args.field]))
-    need += ["rho"] if args.field != "rho" and args.kind == "slice" else []
+    need += ["rho"] if (args.field != "rho" and args.kind == "slice") or (args.field == "rho" and render) else []
     d = _read(args.file, args.step, need)
     dev = torch.device(args.device)
     m = d["m"]
-    if args.field == "rho":
+    if render:
+        # channel 0: kappa m, channel 1: the field. Default kappa: mean optical depth 1 over the box's face
+        a = "xyz".index(args.axis[-1])
+        area = (box.hi[(a + 1) % 3] - box.lo[(a + 1) % 3]) * (box.hi[(a + 2) % 3] - box.lo[(a + 2) % 3])
+        kappa = area / float(np.sum(m, dtype=np.float64)) if args.kappa is None else args.kappa
+        w = [kappa * m, d["rho"] if args.field == "rho" else _quantity(d, args.field)]
+    elif args.field == "rho":
         w = [m]
     else:
         vol = m / d["rho"] if args.kind == "slice" else m
@@ -259,11 +272,13 @@ def cmd_image(args):
     img = sph_image(t(d["x"], torch.float64), t(d["y"], torch.float64), t(d["z"], torch.float64),
                     t(d["h"], torch.float32), t(np.stack(w), torch.float32), box, kind=args.kind, axis=args.axis,
                     res=(args.res, args.res), sinc_index=float(np.ravel(attrs.get("sincIndex", [6.0]))[0]))
-    img = (img[0] if len(w) == 1 else torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))).cpu().numpy()
+    if not render:
+        img = img[0] if len(w) == 1 else torch.where(img[1] != 0, img[0] / img[1], torch.zeros_like(img[0]))
+    img = img.cpu().numpy()
     out = args.out or f"image_{args.field}.npy"
     np.save(out, img)
-    print(f"wrote {out}: {args.kind} of {args.field} along {args.axis}, {img.shape[1]} x {img.shape[0]} pixels, "
-          f"min {img.min():.6e} max {img.max():.6e}")
+    print(f"wrote {out}: {args.kind} of {args.field} along {args.axis}, {img.shape[-1]} x {img.shape[-2]} pixels"
+          f"{f' x [I, T], kappa {kappa:.6e}' if render else ''}, min {img.min():.6e} max {img.max():.6e}")
 
 
 def _snapshot_grid(args, fields):
@@ -486,8 +501,9 @@ def main(argv=None):
     p.add_argument("file")
     p.add_argument("field")
     p.add_argument("-s", "--step", type=int, default=None)
-    p.add_argument("--kind", choices=["slice", "projection"], default="slice")
-    p.add_argument("--axis", default="z", choices=["x", "y", "z"])
+    p.add_argument("--kind", choices=["slice", "projection", "render"], default="slice")
+    p.add_argument("--axis", default="z", choices=["x", "y", "z", "-x", "-y", "-z"])
+    p.add_argument("--kappa", type=float, default=None)
     p.add_argument("--res", type=int, default=512)
     p.add_argument("--device", default="cuda")
     p.add_argument("-o", "--out", default=None)
